@@ -73,7 +73,12 @@ def main():
     ap.add_argument("--plain-3dgs-step", action="store_true", help="config3 / config4: time the vanilla 3DGS step on the config's scene (what rounds 1-4 printed) instead of the step the config defines")
     ap.add_argument("--no-eight-thread-baseline", action="store_true", help="skip the extra 8-thread run of the CPU baseline (BASELINE.md section 2's planned core count)")
     ap.add_argument("--spawn-check", action="store_true", help="only bring the process group up, all-reduce one word and print {n_gpus: world size as seen after init} (tests/test_bench_spawn.py; needs no GPU with SGR_BENCH_BACKEND=gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, run the last timed step once more from the state every "
+                    "run starts from and write what it computed (loss, image, radii, gradient, Adam moments) as DIR/<name>.npy, float32 or "
+                    "float64, at most 64 MB in all: a larger array is cut to a fixed, seeded sample of its elements (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `--gpus N` without a launcher's environment: this process becomes the launcher (one rank per GPU under torch.distributed.run,
     # exactly the command line of the docstring), so a bare `python bench.py --gpus 8` can never run one rank and call it eight
@@ -194,11 +199,11 @@ def main():
     def do_step(tr, s):
         k = cam_index(s)
         if isinstance(tr, NativeTrainer):
-            tr.step(cams_d[k], gts[k], cam_key=k)
+            return tr.step(cams_d[k], gts[k], cam_key=k)
         elif isinstance(tr, CoarseSdfStep):
-            tr.step(cams_d[k], gts[k], k)
+            return tr.step(cams_d[k], gts[k], k)
         else:
-            tr.step(cams_d[k], gts[k])
+            return tr.step(cams_d[k], gts[k])
 
     def sync_all():
         if isinstance(trainer, NativeTrainer):
@@ -233,6 +238,8 @@ def main():
             params.flat.copy_(snap[0]); o.exp_avg.copy_(snap[1]); o.exp_avg_sq.copy_(snap[2])
         o.t = snap[3]
 
+    # (--dump-outputs: the state every run starts from -- the scene as defined, the optimiser before its first step)
+    start = snapshot(trainer) if args.dump_outputs else None
     if args.preroll > 0 and not forward_only:
         snap = snapshot(trainer)
         for s in range(max(args.preroll, len(cams))):
@@ -291,6 +298,20 @@ def main():
     t1 = time.perf_counter()
     mark("after_timed")
     lib.sgr_profile_enable(0)
+    if args.dump_outputs:
+        # The last timed step once more, on its camera, from `start`: the state the timed step itself saw is W + K - 1 steps away
+        # from it, and the float atomics of the backward blend round differently from run to run -- rounding that Adam's
+        # normalised update (eps 1e-15) turns into lr-sized differences within a few steps.  From `start` the same inputs give the
+        # same outputs.  The state after the timed region is put back before anything else runs.
+        after = snapshot(trainer)
+        restore(trainer, start)
+        res = do_step(trainer, args.warmup + args.steps - 1)
+        sync_all()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(trainer, params, opt_state(trainer), res))
+        del res
+        restore(trainer, after)
+        del after, start
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
@@ -856,23 +877,66 @@ class ForwardOnly:
         cm = (grad_sink(binning_capacity=capacity, header_out=self.hdr, header_event=self.ev) if capacity else
               grad_sink(speculative=False) if self.host_sync else contextlib.nullcontext())
         with torch.no_grad(), cm:
-            self.R(st)(t["means3D"], self.m2, t["opacities"], shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
+            return self.R(st)(t["means3D"], self.m2, t["opacities"], shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
 
     def step(self, cam, gt):
+        """(image, radii) of the forward, as the rasterizer returns them"""
         self.calls += 1
         if self.calls <= 8 or self.host_sync:
-            self._forward(cam, 0)
+            out = self._forward(cam, 0)
             self.last_num_rendered = self.cmod.last_forward["num_rendered"]
             self.max_R = max(self.max_R, self.last_num_rendered)
             self.capacity = self.max_R + self.max_R // 4 + 65536
-            return
+            return out
         if self.calls > 9:  # the previous sync-free forward: valid?  (checked one call later: its header has long arrived)
             self.ev.synchronize()
             self.last_num_rendered = int(self.hdr[0]) & 0xFFFFFFFF
             if self.last_num_rendered > self.capacity or int(self.hdr[6]):
                 self.redone += 1
                 self.capacity = self.last_num_rendered + self.last_num_rendered // 2
-        self._forward(cam, self.capacity)
+        return self._forward(cam, self.capacity)
+
+
+def step_outputs(trainer, params, opt, res):
+    """name -> device tensor: what one step computed (`res`: its return value) -- the loss, the rendered image and radii, the
+    gradient of the 11 non-SH floats per Gaussian (the SH gradient never leaves the SH-Adam kernel) and both Adam moments of every
+    parameter.  Not the updated parameters themselves: on a first step Adam moves every parameter with a nonzero gradient by its
+    full learning rate in the gradient's sign, so a gradient within rounding of zero moves it either way from run to run."""
+    from sugar_amd.train_step import NativeTrainer
+    if isinstance(trainer, ForwardOnly):
+        image, radii = res
+        return {"image": image, "radii": radii}
+    out = {}
+    if isinstance(res, tuple):   # ViewShardedTrainer: (loss, render package)
+        res, pkg = res
+        out["image"], out["radii"] = pkg["render"], pkg["radii"]
+    elif isinstance(trainer, NativeTrainer):   # (image and radii stay in the trainer's buffers)
+        out["image"], out["radii"] = trainer.image, trainer.radii
+    out["loss"] = res.reshape(1)
+    grad, m, v = params.split_flat(params.flat_grad), params.split_flat(opt.exp_avg), params.split_flat(opt.exp_avg_sq)
+    for k in params.NAMES:
+        if k != "features":
+            out["grad_" + k] = grad[k]
+        out["exp_avg_" + k], out["exp_avg_sq_" + k] = m[k], v[k]
+    return out
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array: floats as float32 (float64 stays float64), integers as float64 (exact); an array of more
+    elements than its share of DUMP_BYTES is cut to a sample of them, the same sorted seeded indices in every run of a shape"""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // (8 * len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def unmodified_path_legs(scene, cams, gts, bg_d, dev, n_steps):

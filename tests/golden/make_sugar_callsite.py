@@ -23,7 +23,11 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("SUGAR_REFERENCE", "/root/reference")
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from tests import ref_env  # noqa: E402
+
+REF = ref_env.reference_root() or os.environ.get("SUGAR_REFERENCE", "/root/reference")  # (the staged snapshot where the tree is absent)
 W, H, P = 200, 152, 3000
 
 
