@@ -644,6 +644,30 @@ int sgr_splat_mesh_face_verts(int P, const float* points, const float* scaling, 
                               const float* primitive_verts, float triangle_scale, const float* world_to_view,
                               const float* projection, float* face_verts, void* stream);
 
+/* ---- the UV texture of the refined mesh: extract_texture_image_and_uv_from_gaussians, sugar_scene/sugar_model.py:2464-2677 ----------
+ * (csrc/texture.hip; added under ABI version 4, additive).  T triangles, square_size s >= 3, S = sgr_texture_size(T, s) =
+ * s * int(sqrt(T // 2 + 1) + 1) the texture side (S^2 < 2^31); every texture buffer is row-major [S, S(, 3)] in the reference's final
+ * orientation (transposed + flipped).
+ * sgr_texture_atlas: the initial image (:2538-2605) -- per owned texel SH2RGB of the DC feature of the first of the triangle's n Gaussians
+ *   with the largest exp(-|M^T (x - mu)|^2 / 2), 0.5 at unowned texels -- into texture[S,S,3]; counter[S^2] (float) and winner[S^2] are
+ *   zeroed.  verts[V,3], faces[T,3] (int64, a vertex index outside [0, V) gives NaN texels), points[T*n,3], inv_scaled_rot[T*n,3,3]
+ *   (get_covariance(return_full_matrix, return_sqrt, inverse_scales)), features_dc rows of feat_stride floats (first 3 used).
+ * sgr_texture_bake_view: one camera of the baking loop (:2620-2675), claim + apply.  pix_to_face[H,W] (int64, K = 1), bary[H,W,3],
+ *   zbuf[H,W], dists[H,W]: the hard mesh fragments; znear / zfar: the camera's (softmax_rgb_blend); verts_uv[3T,2] with faces_uv =
+ *   arange(3T); rgb: float pixel (y, x) channel c at rgb[y*stride_h + x*stride_w + c*stride_c].  A texel several covered pixels map to
+ *   takes the pixel with the largest row-major index.  view: 0, 1, 2, ... in order, never repeated between two atlas calls (it tags
+ *   winner[], which is therefore never cleared).  No host synchronisation.
+ * sgr_texture_finalize: out[S,S,3] = texture / max(counter, 1). */
+int sgr_texture_size(int T, int square_size);
+int sgr_texture_atlas(int T, int n, int square_size, int V, const float* verts, const int64_t* faces, const float* points,
+                      const float* inv_scaled_rot, const float* features_dc, int feat_stride, int S, float* texture, float* counter,
+                      uint64_t* winner, void* stream);
+int sgr_texture_bake_view(int width, int height, int view, const int64_t* pix_to_face, const float* bary, const float* zbuf,
+                          const float* dists, float znear, float zfar, int T, const float* verts_uv, const float* rgb,
+                          int64_t rgb_stride_h, int64_t rgb_stride_w, int64_t rgb_stride_c, int S, uint64_t* winner,
+                          float* texture, float* counter, void* stream);
+int sgr_texture_finalize(int S, const float* texture, const float* counter, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_gathers=False, patch_densifier=False) -> str:
+def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_gathers=False, patch_densifier=False,
+            patch_texture=False) -> str:
     """Returns "patched" (real pytorch3d found, knn_points redirected) or "shim" (stand-in package activated).
 
     `patch_sugar`: also route SuGaR's own Gaussian-buffer-sharing tensor code -- `get_points_rgb`, `get_covariance(return_sqrt)`,
@@ -34,7 +35,9 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
     `patch_gathers`: `SuGaR.points / scaling / quaternions / get_normals()` return tensors whose row gathers `x[idx]` have a HIP
     backward (sugar_amd.sugar_patch.install_row_gathers); pass the module like `patch_sugar`, or True.
     `patch_densifier`: the per-iteration densification statistics (`SuGaRDensifier.update_densification_stats`,
-    `GaussianModel.add_densification_stats`) without boolean-mask indexing (install_densifier)."""
+    `GaussianModel.add_densification_stats`) without boolean-mask indexing (install_densifier).
+    `patch_texture`: `extract_texture_image_and_uv_from_gaussians` (the refined mesh's UV texture) runs on the HIP kernels of
+    sugar_amd.texture (install_texture); pass the module like `patch_sugar`, or True."""
     real_plyfile = _real_package("plyfile")  # (probed BEFORE the stand-in directory can shadow it on sys.path)
     mode = _install_pytorch3d()
     _install_plyfile(real_plyfile)
@@ -52,7 +55,45 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
         from .. import sugar_patch
         module = importlib.import_module("sugar_scene.sugar_model") if patch_gathers is True else patch_gathers
         sugar_patch.install_row_gathers(module)
+    if patch_texture:
+        install_texture(importlib.import_module("sugar_scene.sugar_model") if patch_texture is True else patch_texture)
     return mode
+
+
+_TEXTURE_FN = "extract_texture_image_and_uv_from_gaussians"
+_TEXTURE_MODULES = ("sugar_extractors.refined_mesh",)   # binds the name at import (`from sugar_scene.sugar_model import ...`)
+
+
+def install_texture(sugar_model_module) -> int:
+    """`patch_texture`: the module-level `extract_texture_image_and_uv_from_gaussians` of `sugar_scene.sugar_model`
+    (sugar_model.py:2464-2677) -- and of `sugar_extractors.refined_mesh` when that module is already imported -- becomes
+    `sugar_amd.texture.extract_texture_image_and_uv_from_gaussians`.  Returns the number of names rebound; `uninstall_texture()`
+    undoes it."""
+    from .. import texture
+    original = getattr(sugar_model_module, _TEXTURE_FN)
+    original = getattr(original, "_sugar_amd_original", original)
+
+    def extract_texture_image_and_uv_from_gaussians(rc, square_size=10, n_sh=-1, texture_with_gaussian_renders=True):
+        return texture.extract_texture_image_and_uv_from_gaussians(rc, square_size, n_sh, texture_with_gaussian_renders)
+    extract_texture_image_and_uv_from_gaussians.__doc__ = texture.extract_texture_image_and_uv_from_gaussians.__doc__
+    extract_texture_image_and_uv_from_gaussians._sugar_amd_original = original
+    count = 0
+    for mod in [sugar_model_module] + [sys.modules[m] for m in _TEXTURE_MODULES if m in sys.modules]:
+        if getattr(mod, _TEXTURE_FN, None) is original or hasattr(getattr(mod, _TEXTURE_FN, None), "_sugar_amd_original"):
+            setattr(mod, _TEXTURE_FN, extract_texture_image_and_uv_from_gaussians)
+            count += 1
+    return count
+
+
+def uninstall_texture() -> int:
+    count = 0
+    for name in ("sugar_scene.sugar_model",) + _TEXTURE_MODULES:
+        mod = sys.modules.get(name)
+        f = getattr(mod, _TEXTURE_FN, None) if mod is not None else None
+        if hasattr(f, "_sugar_amd_original"):
+            setattr(mod, _TEXTURE_FN, f._sugar_amd_original)
+            count += 1
+    return count
 
 
 _LOSS_MODULES = ("sugar_utils.loss_utils", "utils.loss_utils")

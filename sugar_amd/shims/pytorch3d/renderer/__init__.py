@@ -1,7 +1,9 @@
 """`pytorch3d.renderer` as far as SuGaR's train / level-set path needs it: the camera algebra (cameras.py) is functional;
 `TexturesVertex` / `TexturesUV` are containers; `RasterizationSettings` / `MeshRasterizer` / `Fragments` (mesh/) give the hard
 (blur_radius = 0) z-buffer the level-set sampler reads (sugar_scene/sugar_model.py:1880-1893,1927-1928,1966) on the HIP kernel
-of this package (sgr_rasterize_meshes).  Shading / texture sampling stay out of scope."""
+of this package (sgr_rasterize_meshes).  Shading is the subset the texture baking of the refined mesh runs
+(sugar_model.py:2607-2661): `AmbientLights`, `BlendParams` / `softmax_rgb_blend` (blending.py), and a `MeshRenderer` /
+`SoftPhongShader` for ambient lights over `TexturesUV` with nearest sampling (mesh/shader.py, plain torch)."""
 import torch
 
 from .._placeholder import out_of_scope
@@ -64,3 +66,6 @@ PerspectiveCameras = out_of_scope("renderer.PerspectiveCameras")
 
 
 from .mesh import Fragments, MeshRasterizer, RasterizationSettings, rasterize_meshes  # noqa: E402,F401
+from .blending import BlendParams, softmax_rgb_blend  # noqa: E402,F401
+from .lighting import AmbientLights  # noqa: E402,F401
+from .mesh.shader import MeshRenderer, SoftPhongShader  # noqa: E402,F401
