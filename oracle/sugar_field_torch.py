@@ -70,3 +70,174 @@ def level_set_points(all_world_points, closest_gaussians_idx, camera_center, gau
         outputs['normals'] = -torch.nn.functional.normalize(density_grad, dim=-1)
         all_outputs[surface_level] = outputs
     return all_outputs
+
+
+# ---- chunked float64 evaluation with condition magnitudes ---------------------------------------------------------------------
+# The same expressions as density_field / level_set_points above, evaluated in float64 over chunks of samples (or pixels), so that a
+# trainer-sized call (1M samples x 16 neighbours, 2M pixels x 21 samples) fits in a few GB on whichever device the tensors are on.
+# Next to every result it returns a CONDITION MAGNITUDE: the same formula evaluated on absolute values, with every exponential
+# exp(a) replaced by (1 + |a|) exp(a) and |a| itself bounded by the absolute evaluation of its argument.  A float32 evaluation of the
+# formula in any order has an error of at most (a small multiple of) 2^-24 times that magnitude, so bars can be stated per element.
+# Every exponential also carries 2^-100, which stands for float32 underflow (a value below 2^-126 may come out as 0).
+UNDERFLOW = 2.0 ** -100
+CHUNK_ELEMS = 1 << 22   # float64 pair rows per chunk: a few hundred MB of temporaries
+
+
+def _f64(t, dev):
+    return None if t is None else t.to(device=dev, dtype=torch.float64)
+
+
+def add_rows(out, idx, vals, heavy=4096):
+    """out.index_add_(0, idx, vals), with the rows that more than `heavy` entries hit summed by a reduction instead: on a GPU,
+    index_add_'s float64 atomics on one address serialise (a Gaussian in every sample's list)"""
+    cnt = torch.bincount(idx, minlength=out.shape[0])
+    hot = torch.nonzero(cnt > heavy)[:, 0]
+    if hot.numel() == 0:
+        return out.index_add_(0, idx, vals)
+    is_hot = torch.isin(idx, hot)
+    out.index_add_(0, idx[~is_hot], vals[~is_hot])
+    for h in hot.tolist():
+        out[h] += vals[idx == h].sum(dim=0)
+    return out
+
+
+def _pairs(d, Bk, s, factor):
+    """d [..., 3] = x - mu per pair, Bk [..., 3, 3], s [...]: w, q_raw, e, o and their magnitudes W, E, O"""
+    w = (Bk.transpose(-1, -2) @ d[..., None])[..., 0]
+    W = (Bk.abs().transpose(-1, -2) @ d.abs()[..., None])[..., 0]
+    q_raw = (w * w).sum(dim=-1)
+    e = torch.exp(-0.5 * q_raw.clamp(min=0., max=1e8))
+    E = (1. + 0.5 * (W * W).sum(dim=-1)) * e + UNDERFLOW
+    return w, W, q_raw, e, E, factor * s * e, factor * s.abs() * E
+
+
+def density_field_chunked(x, closest_gaussians_idx, gaussian_centers, gaussian_inv_scaled_rotation, gaussian_strengths,
+                          density_factor=1.0, grad_opacities=None, grad_densities=None, chunk=None):
+    """density_field in float64, chunked over samples; with grad_opacities / grad_densities (either may be None), also the gradients of
+    sum(grad_opacities * opacities) + sum(grad_densities * densities) w.r.t. x, centres, B [P,3,3] and strengths [P].
+    Returns a dict of float64 tensors on x's device: opacities, densities, and with gradients dx, dcenters, dB, dstrengths; every
+    entry `k` has its condition magnitude as `k + '_mag'`."""
+    dev = x.device
+    N, K = closest_gaussians_idx.shape
+    P = gaussian_centers.shape[0]
+    ce = _f64(gaussian_centers, dev); Bm = _f64(gaussian_inv_scaled_rotation, dev).reshape(P, 3, 3)
+    st = _f64(gaussian_strengths, dev).reshape(P)
+    xs = _f64(x, dev); nb = closest_gaussians_idx.to(dev)
+    go_all, gd_all = _f64(grad_opacities, dev), _f64(grad_densities, dev)
+    grads = go_all is not None or gd_all is not None
+    f = float(density_factor)
+    z = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
+    out = dict(opacities=z(N, K), opacities_mag=z(N, K), densities=z(N), densities_mag=z(N))
+    if grads:
+        out.update(dx=z(N, 3), dx_mag=z(N, 3), dcenters=z(P, 3), dcenters_mag=z(P, 3), dB=z(P, 9), dB_mag=z(P, 9),
+                   dstrengths=z(P), dstrengths_mag=z(P))
+    step = max(1, (chunk or CHUNK_ELEMS) // max(K, 1))
+    for a in range(0, N, step):
+        b = min(N, a + step)
+        idx = nb[a:b]
+        Bk = Bm[idx]
+        d = xs[a:b, None] - ce[idx]
+        D = d.abs()
+        w, W, q_raw, e, E, o, O = _pairs(d, Bk, st[idx], f)
+        out["opacities"][a:b] = o; out["opacities_mag"][a:b] = O
+        out["densities"][a:b] = o.sum(dim=-1); out["densities_mag"][a:b] = O.sum(dim=-1)
+        if not grads:
+            continue
+        go = z(b - a, K); G = z(b - a, K)
+        if go_all is not None:
+            go = go + go_all[a:b]; G = G + go_all[a:b].abs()
+        if gd_all is not None:
+            go = go + gd_all[a:b, None]; G = G + gd_all[a:b, None].abs()
+        inside = (q_raw >= 0.) & (q_raw <= 1e8)   # torch.clamp passes the gradient on the closed range
+        dq = torch.where(inside, -0.5 * f * st[idx] * e * go, torch.zeros_like(e))
+        DQ = 0.5 * f * st[idx].abs() * E * G
+        dw = 2. * w * dq[..., None]; DW = 2. * W * DQ[..., None]
+        dd = (Bk @ dw[..., None])[..., 0]; DD = (Bk.abs() @ DW[..., None])[..., 0]
+        out["dx"][a:b] = dd.sum(dim=1); out["dx_mag"][a:b] = DD.sum(dim=1)
+        fl = idx.reshape(-1)
+        add_rows(out["dcenters"], fl, -dd.reshape(-1, 3)); add_rows(out["dcenters_mag"], fl, DD.reshape(-1, 3))
+        add_rows(out["dB"], fl, (d[..., :, None] * dw[..., None, :]).reshape(-1, 9))
+        add_rows(out["dB_mag"], fl, (D[..., :, None] * DW[..., None, :]).reshape(-1, 9))
+        add_rows(out["dstrengths"], fl, (go * f * e).reshape(-1))
+        add_rows(out["dstrengths_mag"], fl, (G * f * E).reshape(-1))
+    if grads:
+        out["dB"] = out["dB"].reshape(P, 3, 3); out["dB_mag"] = out["dB_mag"].reshape(P, 3, 3)
+    return out
+
+
+def level_set_points_chunked(all_world_points, closest_gaussians_idx, camera_center, gaussian_centers, gaussian_inv_scaled_rotation,
+                             gaussian_strengths, gaussian_standard_deviations, surface_levels=(0.1, 0.3, 0.5), n_points_in_range=21,
+                             range_size=3., density_factor=1., chunk=None):
+    """level_set_points in float64, chunked over pixels, on every pixel (not only the valid ones).  Returns a dict on the points'
+    device with
+      densities [N, R], densities_mag [N, R]: the sample densities after the >= 1 normalisation, and their condition magnitudes
+        (each sample's distance to its neighbours counts |p - mu| + |t| |dir| per axis: the sample point is p + t dir);
+      t [N, R]: the sample offsets along the ray; dir [N, 3]: the unit ray;
+      levels: {level: dict(valid [N] bool, first [N] int64 (the reference's first_point_above_level), points [N, 3],
+               normals [N, 3], grad [N, 3] (the unnormalised density gradient at the point), grad_mag [N, 3],
+               hess_mag [N] (sum over neighbours of o (|B|_F^2 + |B w|^2), a bound on the Frobenius norm of the density's Hessian))}
+    Invalid pixels have zero points, normals and gradients."""
+    dev = all_world_points.device
+    N, K = closest_gaussians_idx.shape
+    P = gaussian_centers.shape[0]
+    R = int(n_points_in_range)
+    wp = _f64(all_world_points, dev); nb = closest_gaussians_idx.to(dev)
+    ce = _f64(gaussian_centers, dev); Bm = _f64(gaussian_inv_scaled_rotation, dev).reshape(P, 3, 3)
+    st = _f64(gaussian_strengths, dev).reshape(P); gs = _f64(gaussian_standard_deviations, dev).reshape(-1)
+    cam = _f64(camera_center, dev).reshape(1, 3)
+    f = float(density_factor)
+    z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=dev)
+    rng = torch.linspace(-range_size, range_size, R).to(device=dev, dtype=torch.float64)   # the reference's float32 grid, :1976
+    out = dict(densities=z(N, R), densities_mag=z(N, R), t=z(N, R), dir=z(N, 3), levels={})
+    for L in surface_levels:
+        out["levels"][L] = dict(valid=z(N, dt=torch.bool), first=z(N, dt=torch.int64), points=z(N, 3), normals=z(N, 3),
+                                grad=z(N, 3), grad_mag=z(N, 3), hess_mag=z(N))
+    step = max(1, (chunk or CHUNK_ELEMS) // max(K * R, 1))
+    for a in range(0, N, step):
+        b = min(N, a + step)
+        idx = nb[a:b]
+        p = wp[a:b]
+        dirs = torch.nn.functional.normalize(p - cam, dim=-1)
+        t = rng[None, :] * gs[idx[:, 0]][:, None]                                    # [n, R]
+        samples = p[:, None, :] + t[..., None] * dirs[:, None, :]                     # [n, R, 3]
+        mu, Bk, s = ce[idx][:, None], Bm[idx][:, None], st[idx][:, None]              # [n, 1, K, ...]
+        d = samples[:, :, None, :] - mu                                               # [n, R, K, 3]
+        D = (p[:, None, :] - ce[idx]).abs()[:, None] + (t[..., None] * dirs[:, None, :]).abs()[:, :, None, :]
+        W = (Bk.abs().transpose(-1, -2) @ D[..., None])[..., 0]
+        w = (Bk.transpose(-1, -2) @ d[..., None])[..., 0]
+        e = torch.exp(-0.5 * (w * w).sum(dim=-1).clamp(min=0., max=1e8))
+        E = (1. + 0.5 * (W * W).sum(dim=-1)) * e + UNDERFLOW
+        dens = (f * s * e).sum(dim=-1)
+        dmag = (f * s.abs() * E).sum(dim=-1)
+        m = dens >= 1.
+        dens = torch.where(m, dens / (dens + 1e-12), dens)
+        out["densities"][a:b] = dens; out["densities_mag"][a:b] = dmag; out["t"][a:b] = t; out["dir"][a:b] = dirs
+        for L, lo in out["levels"].items():
+            under = dens - L < 0
+            above = dens - L > 0
+            _, first = above.max(dim=-1)
+            valid = under[:, 0] & (first != 0)
+            fc = first.clamp(min=1)
+            d_first = dens.gather(1, fc[:, None])[:, 0]; d_prev = dens.gather(1, fc[:, None] - 1)[:, 0]
+            t_first = t.gather(1, fc[:, None])[:, 0]; t_prev = t.gather(1, fc[:, None] - 1)[:, 0]
+            den = torch.where(valid, d_first - d_prev, torch.ones_like(d_first))
+            ti = (L - d_prev) / den * (t_first - t_prev) + t_prev
+            pts = p + ti[:, None] * dirs
+            dq = pts[:, None, :] - ce[idx]                                            # [n, K, 3]
+            wq = (Bm[idx].transpose(-1, -2) @ dq[..., None])[..., 0]
+            Wq = (Bm[idx].abs().transpose(-1, -2) @ dq.abs()[..., None])[..., 0]
+            eq = torch.exp(-0.5 * (wq * wq).sum(dim=-1).clamp(min=0., max=1e8))
+            Eq = (1. + 0.5 * (Wq * Wq).sum(dim=-1)) * eq + UNDERFLOW
+            oq = f * st[idx] * eq
+            Bw = (Bm[idx] @ wq[..., None])[..., 0]
+            grad = (oq[..., None] * Bw).sum(dim=1)
+            gmag = (f * st[idx].abs()[..., None] * Eq[..., None] * (Bm[idx].abs() @ Wq[..., None])[..., 0]).sum(dim=1)
+            hess = (oq.abs() * ((Bm[idx] ** 2).sum(dim=(-1, -2)) + (Bw * Bw).sum(dim=-1))).sum(dim=1)
+            v = valid[:, None]
+            lo["valid"][a:b] = valid; lo["first"][a:b] = first
+            lo["points"][a:b] = torch.where(v, pts, torch.zeros_like(pts))
+            lo["normals"][a:b] = torch.where(v, -torch.nn.functional.normalize(grad, dim=-1), torch.zeros_like(grad))
+            lo["grad"][a:b] = torch.where(v, grad, torch.zeros_like(grad))
+            lo["grad_mag"][a:b] = torch.where(v, gmag, torch.zeros_like(gmag))
+            lo["hess_mag"][a:b] = torch.where(valid, hess, torch.zeros_like(hess))
+    return out

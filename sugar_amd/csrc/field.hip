@@ -891,8 +891,9 @@ int sgr_density_field_backward_gather(int N, int K, int P, const float* x, const
                                       float* dL_dinv_scaled_rot, float* dL_dstrengths, char* scratch, const float* packed, void* stream)
 {
     if (P <= 0) return 0;
-    if (N < 0 || K <= 0 || (N > 0 && (!x || !nbr_idx)) || !centers || !inv_scaled_rot || !strengths || !dL_dcenters ||
-        !dL_dinv_scaled_rot || !dL_dstrengths || !scratch || (!dL_dopacities && !dL_ddensity) || (size_t)N * K > 0xFFFFFFFFull)
+    // (N == 0: no pair reads a gradient, and empty tensors hand NULL for both -- every output row is written as 0)
+    if (N < 0 || K <= 0 || (N > 0 && (!x || !nbr_idx || (!dL_dopacities && !dL_ddensity))) || !centers || !inv_scaled_rot ||
+        !strengths || !dL_dcenters || !dL_dinv_scaled_rot || !dL_dstrengths || !scratch || (size_t)N * K > 0xFFFFFFFFull)
         return SGR_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const size_t nk = (size_t)N * K, pa = sgr_align(((size_t)P + 1) * 4);
