@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: 3DGS/SuGaR train step on 1M Gaussians @ 1920x1080 (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +12,19 @@ plus the 11 non-SH gradient floats per Gaussian (all-reduce) over RCCL; the SH g
 the Adam kernel of every rank
 ("weak" scaling: one view per GPU per step; value = views/s over all ranks).
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up (scene, targets, the untimed pre-roll),
+W warm-up steps, the K timed steps, `--dump-outputs` if given, and the line -- the contract fields plus how the number was
+taken (config, host enqueue time, forwards repeated).  With `--full` the run goes on behind the timed region with every
+other measurement and check, and the line carries besides
   roofline     -- forward blend kernel (the kernel BASELINE.json grades): algorithmic bytes / HIP-event time
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference rasterizer) on the host cores, rasterizer
                   forward+backward of ONE view of the same workload
   stages_ms    -- per-stage HIP-event averages of the rasterizer, ms_fwd_bwd = their sum (taken in an untimed pass over
                   the same cameras after the timed region: event pairs cost GPU pipeline time, so inside the timed region
-                  only the graded kernel is bracketed).
+                  only the graded kernel is bracketed)
+  and what the legs behind the graded region measure (densify_stats_variant, fast_alpha_variant, after_training,
+  many_cameras_shuffled, the unmodified caller's ms_fwd_bwd_api / vs_reference_same_gpu / reference_loop, with several ranks
+  the collectives' cost), each of which its own switch skips (--no-densify-variant, --drift-steps 0, --cameras 0, ...).
 """
 from __future__ import annotations
 
@@ -47,6 +53,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every other measurement and check (per-stage times, "
+                    "rooflines, the CPU baseline, the legs behind the graded region); a plain run prints the headline and stops")
     ap.add_argument("--workload", default="metric", help="synthetic config name (sugar_amd/synthetic.py)")
     ap.add_argument("--gaussians", type=int, default=None, help="override the Gaussian count (debug only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -68,7 +76,7 @@ def main():
     ap.add_argument("--host-sync", action="store_true", help="forward with the host round trip for num_rendered (A/B of the sync-free forward)")
     ap.add_argument("--cameras", type=int, default=200, help="hint-robustness leg (untimed, behind the graded region, from the drifted state): this many scattered cameras visited in shuffled order, as a real capture's training views are; 0: skip")
     ap.add_argument("--no-reference-loop", action="store_true", help="skip the untimed legs behind the graded region: the reference's own loop (train.py) on the drop-in rasterizer, the through-API fwd+bwd time, and the same-GPU A/B against the reference's kernels")
-    ap.add_argument("--reference-loop", action="store_true", help="(default behaviour, kept as an explicit switch) run those legs")
+    ap.add_argument("--reference-loop", action="store_true", help="(default behaviour of --full, kept as an explicit switch) run those legs")
     ap.add_argument("--reference-loop-steps", type=int, default=24)
     ap.add_argument("--plain-3dgs-step", action="store_true", help="config3 / config4: time the vanilla 3DGS step on the config's scene (what rounds 1-4 printed) instead of the step the config defines")
     ap.add_argument("--no-eight-thread-baseline", action="store_true", help="skip the extra 8-thread run of the CPU baseline (BASELINE.md section 2's planned core count)")
@@ -316,6 +324,80 @@ def main():
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
+
+    def headline():
+        """the line's fields a plain run prints: the contract fields and how the timed steps were taken"""
+        K = args.steps
+        out = {
+            "metric": "train_step_images_per_sec",
+            "value": world * K / elapsed,
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / K,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "data_note": "targets = the same views rendered from a jittered copy of the scene (bench.py: make_target_renderer)",
+            "config": {
+                "workload": (f"{args.workload}: {P} Gaussians @ {W}x{H}, SH degree 3, rasterizer FORWARD only through the "
+                             "reference-shaped API, 8 orbit cameras cycled" if forward_only else
+                             f"{args.workload}: {P} Gaussians @ {W}x{H}, SuGaR coarse-SDF-shaped step (coarse_sdf.py:51,575-597; "
+                             "SURVEY 8d config 3): SH->RGB (sh_levels 4) -> raster fwd with colors_precomp -> 0.8 L1 + 0.2 DSSIM; "
+                             "view depth as colour, bg = max depth -> raster fwd -> L1 on the depth map; ONE backward through both "
+                             "(2 raster fwd + 2 raster bwd) -> Adam over 59 floats/Gaussian, 8 orbit cameras cycled" if coarse_sdf else
+                             f"{args.workload}: {P} FLAT Gaussians bound to a {P}-triangle surface mesh (sugar_model.py:149-228, 438-442: "
+                             "first scale = extent / 1e6) @ " + f"{W}x{H}, SH degree 3: 3DGS train step (raster fwd -> 0.8 L1 + 0.2 DSSIM -> bwd "
+                             "-> Adam) + ONE level-set sampling pass of the coarse-mesh extractor for the same view (depth render -> 124k "
+                             "pixels -> k-NN(16) -> 21 samples x 16 neighbours x 3 levels, sugar_model.py:1848-2083), 8 orbit cameras cycled"
+                             if refine_cfg else
+                             f"{args.workload}: {P} Gaussians @ {W}x{H}, SH degree 3, 3DGS train step "
+                             "(raster fwd -> 0.8 L1 + 0.2 DSSIM -> bwd -> Adam, 59 floats/Gaussian), 8 orbit cameras cycled"),
+                "step_driver": ("reference-shaped Python API" if forward_only else
+                                "reference-shaped Python API + autograd (sugar_amd.shcolor, diff_gaussian_rasterization, fused_loss, FlatAdam)"
+                                + (", host round trip for num_rendered in every forward" if trainer.host_sync else
+                                   ", speculative sync-free forwards (header checked at the end of the call)") if coarse_sdf else
+                                "native (sgr_trainer_step: one call per step, sync-free forward, walk hint "
+                                + ("on" if getattr(trainer, "walk_hint", False) else "off") + ", blend launch order "
+                                + ("by depth" if getattr(trainer, "launch_order", False) else "raster") + ")" if native
+                                else "python (autograd-based ViewShardedTrainer)"),
+                "views_per_step": world,
+                "parallelism": (f"view-sharded dp{world}: all-gather of 3 masked colour grads per Gaussian and view + all-reduce of "
+                                "the 11 non-SH floats per Gaussian (RCCL), SH gradient summed over views inside the Adam kernel"
+                                if getattr(trainer, 'compact_sh', True) and world > 1 else f"view-sharded dp{world}" if world > 1
+                                else f"view-sharded dp{world}, single process, no collective"),
+            },
+            # wall time of the host loop; the native trainer spends most of it WAITING for the previous step's header (it runs one
+            # step ahead of the GPU by design): host_work_ms_per_step is what it actually computes and enqueues
+            "host_enqueue_ms_per_step": 1e3 * (t_enq - t0) / K,
+            "host_work_ms_per_step": (1e3 * (hw1 - hw0) / K) if isinstance(trainer, NativeTrainer) else None,
+            "exact_alpha": bool(lib.sgr_get_exact_alpha()),
+        }
+        if getattr(trainer, "exchange", False):
+            out["config"]["collectives"] = ("forced on a one-rank RCCL group" if world == 1 else ("RCCL" if backend == "nccl" else backend + " (functional rehearsal: ranks share a GPU)")) + \
+                (", enqueued by the library (sgr_trainer_step_exchange)" if getattr(trainer, "native_collectives", False) else ", torch.distributed between four phase calls")
+        if forward_only:
+            # (a sync-free forward that outgrew its capacity returns at once and would be timed as an abnormally fast step)
+            out["forwards_invalid"] = trainer.redone
+            out["config"]["step_driver"] += " (host round trip for num_rendered every call, no extension)" if trainer.host_sync else " (sync-free after one pass over the cameras)"
+        if isinstance(trainer, NativeTrainer):
+            out["forwards_repeated"] = {"in_timed_region": marks.get("after_timed", 0) - marks.get("after_warmup", 0),
+                                        "pre_roll_and_warmup": marks.get("after_warmup", 0), "whole_run": trainer.redone,
+                                        "tiles_repaired_in_place_whole_run": trainer.repaired_tiles}
+        return out
+
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(headline()) + "\n").encode())
+        if use_group:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     ms = (C.c_double * len(STAGES))()
     cnt = (C.c_int64 * len(STAGES))()
     lib.sgr_profile_read(ms, cnt, len(STAGES))
@@ -520,54 +602,10 @@ def main():
                                 "source": pj.get("valu_source")}
             except Exception:
                 traffic = None
-        out = {
-            "metric": "train_step_images_per_sec",
-            "value": world * K / elapsed,
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / K,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "data_note": "targets = the same views rendered from a jittered copy of the scene (bench.py: make_target_renderer)",
-            "config": {
-                "workload": (f"{args.workload}: {P} Gaussians @ {W}x{H}, SH degree 3, rasterizer FORWARD only through the "
-                             "reference-shaped API, 8 orbit cameras cycled" if forward_only else
-                             f"{args.workload}: {P} Gaussians @ {W}x{H}, SuGaR coarse-SDF-shaped step (coarse_sdf.py:51,575-597; "
-                             "SURVEY 8d config 3): SH->RGB (sh_levels 4) -> raster fwd with colors_precomp -> 0.8 L1 + 0.2 DSSIM; "
-                             "view depth as colour, bg = max depth -> raster fwd -> L1 on the depth map; ONE backward through both "
-                             "(2 raster fwd + 2 raster bwd) -> Adam over 59 floats/Gaussian, 8 orbit cameras cycled" if coarse_sdf else
-                             f"{args.workload}: {P} FLAT Gaussians bound to a {P}-triangle surface mesh (sugar_model.py:149-228, 438-442: "
-                             "first scale = extent / 1e6) @ " + f"{W}x{H}, SH degree 3: 3DGS train step (raster fwd -> 0.8 L1 + 0.2 DSSIM -> bwd "
-                             "-> Adam) + ONE level-set sampling pass of the coarse-mesh extractor for the same view (depth render -> 124k "
-                             "pixels -> k-NN(16) -> 21 samples x 16 neighbours x 3 levels, sugar_model.py:1848-2083), 8 orbit cameras cycled"
-                             if refine_cfg else
-                             f"{args.workload}: {P} Gaussians @ {W}x{H}, SH degree 3, 3DGS train step "
-                             "(raster fwd -> 0.8 L1 + 0.2 DSSIM -> bwd -> Adam, 59 floats/Gaussian), 8 orbit cameras cycled"),
-                "step_driver": ("reference-shaped Python API" if forward_only else
-                                "reference-shaped Python API + autograd (sugar_amd.shcolor, diff_gaussian_rasterization, fused_loss, FlatAdam)"
-                                + (", host round trip for num_rendered in every forward" if trainer.host_sync else
-                                   ", speculative sync-free forwards (header checked at the end of the call)") if coarse_sdf else
-                                "native (sgr_trainer_step: one call per step, sync-free forward, walk hint "
-                                + ("on" if getattr(trainer, "walk_hint", False) else "off") + ", blend launch order "
-                                + ("by depth" if getattr(trainer, "launch_order", False) else "raster") + ")" if native
-                                else "python (autograd-based ViewShardedTrainer)"),
-                "views_per_step": world,
-                "parallelism": (f"view-sharded dp{world}: all-gather of 3 masked colour grads per Gaussian and view + all-reduce of "
-                                "the 11 non-SH floats per Gaussian (RCCL), SH gradient summed over views inside the Adam kernel"
-                                if getattr(trainer, 'compact_sh', True) and world > 1 else f"view-sharded dp{world}" if world > 1
-                                else f"view-sharded dp{world}, single process, no collective"),
-                "instances_per_view": R, "instances_walked_fwd": R_f, "instances_walked_bwd": R_b,
-            },
+        out = headline()
+        out["config"].update(instances_per_view=R, instances_walked_fwd=R_f, instances_walked_bwd=R_b)
+        out.update({
             "ms_fwd_bwd": sum(stages[n] for n in RASTER_STAGES),
-            # wall time of the host loop; the native trainer spends most of it WAITING for the previous step's header (it runs one
-            # step ahead of the GPU by design): host_work_ms_per_step is what it actually computes and enqueues
-            "host_enqueue_ms_per_step": 1e3 * (t_enq - t0) / K,
-            "host_work_ms_per_step": (1e3 * (hw1 - hw0) / K) if isinstance(trainer, NativeTrainer) else None,
             "stages_ms": stages,
             # every launch of the native step sits inside one stage: their sum against the step time of the timed region
             # (the stage times come from the untimed pass with an event pair around every stage; the pairs themselves cost
@@ -583,7 +621,7 @@ def main():
                 "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": blend_ms,
                 "pair_evals_per_s": (256.0 * R_f) / (blend_ms * 1e-3) if blend_ms > 0 else 0.0,
             },
-        }
+        })
         if valu is not None:
             out["roofline_valu"] = valu
         out["roofline"]["kernel"] = "k_blend_fwd_wx" if lib.sgr_get_exact_alpha() else "k_blend_fwd_w"
@@ -607,7 +645,6 @@ def main():
                              "ranges / radii / num_rendered / final_T / n_contrib bit-exact; image <= 5e-7 norm-wise; every gradient tensor <= 1e-5 "
                              "norm-wise AND >= 99.9 % of its elements within 1e-4 relative (floor 1e-3 of the tensor's largest magnitude), next "
                              "to the reference's own run-to-run spread from float atomics (~2e-6)")
-        out["exact_alpha"] = bool(lib.sgr_get_exact_alpha())
         out["parity_unpinned"] = ("not on this line's path, stated for completeness: the mesh z-buffer behind pytorch3d.renderer.MeshRasterizer "
                                   "(csrc/mesh_raster.hip, the coarse-mesh sampler's default depth path) is bit-exact against oracle/mesh_rasterizer.c, "
                                   "which RESTATES pytorch3d 0.7.4 -- absent from the image, so nothing checks it against pytorch3d itself")
@@ -621,16 +658,8 @@ def main():
                 print(f"[bench] the stages sum to {out['stages_cover_frac']:.3f} of the step: something in the step is not inside a stage "
                       "(or the GPU idles between launches)", file=sys.stderr)
         out.update(extras)
-        if forward_only:
-            # (a sync-free forward that outgrew its capacity returns at once and would be timed as an abnormally fast step)
-            out["forwards_invalid"] = trainer.redone
-            out["config"]["step_driver"] += " (host round trip for num_rendered every call, no extension)" if trainer.host_sync else " (sync-free after one pass over the cameras)"
-        if isinstance(trainer, NativeTrainer):
-            out["forwards_repeated"] = {"in_timed_region": marks.get("after_timed", 0) - marks.get("after_warmup", 0),
-                                        "pre_roll_and_warmup": marks.get("after_warmup", 0), "whole_run": trainer.redone,
-                                        "tiles_repaired_in_place_whole_run": trainer.repaired_tiles}
-            if list_write is not None:
-                out["list_write_pass"] = list_write
+        if list_write is not None:
+            out["list_write_pass"] = list_write
         if comm is not None:
             out.update(comm)
             n_small = int(getattr(params, "n_small", 11 * P))
@@ -640,8 +669,6 @@ def main():
                 "all_reduce_ring_wire": int(2 * 4 * n_small * (world - 1) / max(world, 1)),
                 "what": "per step: masked colour gradients + camera centre row of every view (all-gather), the 11 non-SH floats per "
                         "Gaussian (all-reduce; ring wire bytes = 2 (N-1)/N x buffer)"}
-            out["config"]["collectives"] = ("forced on a one-rank RCCL group" if world == 1 else ("RCCL" if backend == "nccl" else backend + " (functional rehearsal: ranks share a GPU)")) + \
-                (", enqueued by the library (sgr_trainer_step_exchange)" if getattr(trainer, "native_collectives", False) else ", torch.distributed between four phase calls")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, cams[0], bg, forward_only, mode="coarse_sdf" if coarse_sdf else "sh",
                                                eight_threads=not args.no_eight_thread_baseline)
