@@ -668,6 +668,40 @@ int sgr_texture_bake_view(int width, int height, int view, const int64_t* pix_to
                           float* texture, float* counter, void* stream);
 int sgr_texture_finalize(int S, const float* texture, const float* counter, float* out, void* stream);
 
+/* ---- the refine stage's mesh binding: SuGaR.points / .scaling / .quaternions of a model bound to a surface mesh ------------------------
+ * (csrc/mesh_bind.hip; sugar_scene/sugar_model.py:383-479, the `not editable` branch; added under ABI version 4, additive).
+ * F faces, n Gaussians per face, V vertices; Gaussian g = f * n + k.  verts[V,3], faces[F,3] (int32; a vertex index outside [0, V) gives
+ * NaN for the elements of that face, never an out-of-bounds access), bary[n,3], scales[F*n,2] (in-plane log-scales), complex_numbers
+ * [F*n,2] (the in-plane rotation, not normalised), thickness[1] (a DEVICE scalar: reading it on the host would synchronise).
+ * sgr_mesh_bind_forward: any of the three outputs may be NULL and is then not computed (nor are the inputs only it needs read):
+ *   points[F*n,3]      = sum_c verts[faces[f,c]] * bary[k,c], c = 0, 1, 2 in order;
+ *   scaling[F*n,3]     = (thickness, exp(scales[g,0]), exp(scales[g,1]));
+ *   quaternions[F*n,4] = normalize(matrix_to_quaternion([R_0 | R_1 | R_2])), R_0 the face normal (divided by max(length, 1e-6), then
+ *                        normalised), R_1 / R_2 the frame (normalize(v0 - v1), normalize(R_0 x that)) turned by normalize(complex).
+ * sgr_mesh_bind_backward: cotangents dL_dpoints / dL_dscaling / dL_dquaternions (each may be NULL = absent) -> dL_dscales[F*n,2] (written
+ *   when dL_dscaling is given), dL_dcomplex[F*n,2] (when dL_dquaternions is given), dL_dverts[V,3] (when dL_dpoints or dL_dquaternions is
+ *   given: OVERWRITTEN with the sum of both paths).  The vertex gradient is deterministic: the per-(face, corner) contributions go to
+ *   contrib[3F,3] (scratch) and vertex v adds contrib[vert_items[i]] for i in [vert_offsets[v], vert_offsets[v+1]) in that order
+ *   (vert_offsets[V+1], vert_items[3F] with item = 3 f + corner: the vertex -> (face, corner) CSR list, built once per topology).
+ * ---- pytorch3d.loss.mesh_normal_consistency of one mesh over a precomputed pair list -------------------------------------------------
+ * pairs[n_pairs,4] (int32): v0, v1 (the shared edge), a, b (the opposite vertices of the two faces).
+ * sgr_normal_consistency_forward: loss[1] = mean over pairs of 1 - cos(n0, n1), n0 = (v1-v0) x (a-v0), n1 = -(v1-v0) x (b-v0), the cosine
+ *   as torch.cosine_similarity (eps = 1e-8); a fixed-shape two-stage reduction in double; scratch: sgr_normal_consistency_scratch_bytes().
+ * sgr_normal_consistency_backward: grad_loss[1] (device) -> dL_dverts[V,3] (overwritten), through contrib[4 n_pairs,3] (scratch) and the
+ *   vertex -> (pair, slot) CSR list vert_offsets[V+1], vert_items[4 n_pairs] (item = 4 p + slot, slots v0, v1, a, b), as above.
+ * No call synchronises with the host. */
+int sgr_mesh_bind_forward(int F, int n, int V, const float* verts, const int32_t* faces, const float* bary, const float* scales,
+                          const float* complex_numbers, const float* thickness, float* points, float* scaling, float* quaternions,
+                          void* stream);
+int sgr_mesh_bind_backward(int F, int n, int V, const float* verts, const int32_t* faces, const float* bary, const float* scales,
+                           const float* complex_numbers, const float* dL_dpoints, const float* dL_dscaling, const float* dL_dquaternions,
+                           const int32_t* vert_offsets, const int32_t* vert_items, float* contrib, float* dL_dverts, float* dL_dscales,
+                           float* dL_dcomplex, void* stream);
+size_t sgr_normal_consistency_scratch_bytes(void);
+int sgr_normal_consistency_forward(int n_pairs, int V, const float* verts, const int32_t* pairs, void* scratch, float* loss, void* stream);
+int sgr_normal_consistency_backward(int n_pairs, int V, const float* verts, const int32_t* pairs, const float* grad_loss,
+                                    const int32_t* vert_offsets, const int32_t* vert_items, float* contrib, float* dL_dverts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

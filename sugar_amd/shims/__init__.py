@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_gathers=False, patch_densifier=False,
-            patch_texture=False) -> str:
+            patch_texture=False, patch_binding=False) -> str:
     """Returns "patched" (real pytorch3d found, knn_points redirected) or "shim" (stand-in package activated).
 
     `patch_sugar`: also route SuGaR's own Gaussian-buffer-sharing tensor code -- `get_points_rgb`, `get_covariance(return_sqrt)`,
@@ -37,7 +37,10 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
     `patch_densifier`: the per-iteration densification statistics (`SuGaRDensifier.update_densification_stats`,
     `GaussianModel.add_densification_stats`) without boolean-mask indexing (install_densifier).
     `patch_texture`: `extract_texture_image_and_uv_from_gaussians` (the refined mesh's UV texture) runs on the HIP kernels of
-    sugar_amd.texture (install_texture); pass the module like `patch_sugar`, or True."""
+    sugar_amd.texture (install_texture); pass the module like `patch_sugar`, or True.
+    `patch_binding`: the refine stage's mesh binding -- `SuGaR.points / scaling / quaternions` of a model bound to a surface mesh -- and
+    the stand-in `pytorch3d.loss.mesh_normal_consistency` of a single mesh run on the HIP kernels of sugar_amd.mesh_bind
+    (install_binding); pass the module like `patch_sugar`, or True."""
     real_plyfile = _real_package("plyfile")  # (probed BEFORE the stand-in directory can shadow it on sys.path)
     mode = _install_pytorch3d()
     _install_plyfile(real_plyfile)
@@ -57,7 +60,41 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
         sugar_patch.install_row_gathers(module)
     if patch_texture:
         install_texture(importlib.import_module("sugar_scene.sugar_model") if patch_texture is True else patch_texture)
+    if patch_binding:
+        install_binding(importlib.import_module("sugar_scene.sugar_model") if patch_binding is True else patch_binding)
     return mode
+
+
+def _loss_standin():
+    """the stand-in `pytorch3d.loss` module if that is what `pytorch3d.loss` resolves to, else None (a real pytorch3d keeps its own)"""
+    try:
+        mod = importlib.import_module("pytorch3d.loss")
+    except ImportError:
+        return None
+    return mod if hasattr(mod, "USE_HIP_NORMAL_CONSISTENCY") else None
+
+
+def install_binding(sugar_model_module) -> int:
+    """`patch_binding`: `sugar_amd.sugar_patch.install_binding` on the module's `SuGaR` class, and the switch of the stand-in
+    `pytorch3d.loss.mesh_normal_consistency` (sugar_trainers/refine.py:776-783).  Returns the number of bindings made (3 properties
+    + 1 when the loss stand-in is the active `pytorch3d.loss`); `uninstall_binding` undoes it."""
+    from .. import sugar_patch
+    count = len(sugar_patch.install_binding(sugar_model_module))
+    loss = _loss_standin()
+    if loss is not None:
+        loss.USE_HIP_NORMAL_CONSISTENCY = True
+        count += 1
+    return count
+
+
+def uninstall_binding(sugar_model_module=None) -> None:
+    from .. import sugar_patch
+    module = sugar_model_module if sugar_model_module is not None else sys.modules.get("sugar_scene.sugar_model")
+    if module is not None:
+        sugar_patch.uninstall_binding(module)
+    loss = _loss_standin()
+    if loss is not None:
+        loss.USE_HIP_NORMAL_CONSISTENCY = False
 
 
 _TEXTURE_FN = "extract_texture_image_and_uv_from_gaussians"

@@ -29,10 +29,24 @@ def _face_pairs_by_edge(edge_of_incidence: torch.Tensor):
     return torch.cat(pairs, dim=0)
 
 
+# Set by sugar_amd.shims.install(patch_binding=...): a single mesh on a ROCm device goes to the HIP kernels of sugar_amd.mesh_bind (the
+# same definition over a pair list that is built once per faces tensor).  Off by default.
+USE_HIP_NORMAL_CONSISTENCY = False
+
+
+def _on_rocm_f32(t):
+    return t.is_cuda and t.dtype == torch.float32
+
+
 def mesh_normal_consistency(meshes):
     if meshes.isempty():
         return torch.tensor([0.0], dtype=torch.float32, device=meshes.device, requires_grad=True)
     N = len(meshes)
+    if USE_HIP_NORMAL_CONSISTENCY and N == 1 and _on_rocm_f32(meshes.verts_list()[0]):
+        from sugar_amd import mesh_bind
+        # the faces tensor the caller built the mesh from (SuGaR.surface_mesh hands over the model's own `_surface_mesh_faces` every
+        # iteration, sugar_model.py:552-560): the topology cache is keyed by it, so it is built once, int32 faces included
+        return mesh_bind.normal_consistency(meshes.verts_list()[0], getattr(meshes, "_faces_given", meshes.faces_list())[0])
     verts = meshes.verts_packed()
     faces = meshes.faces_packed()
     edges = meshes.edges_packed()

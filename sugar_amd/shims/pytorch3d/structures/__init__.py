@@ -30,6 +30,7 @@ class Meshes:
                 raise ValueError("Meshes: expected verts [V,3] and faces [F,3]")
         self._verts = list(verts)
         self._faces = [f.long() for f in faces]
+        self._faces_given = list(faces)   # the caller's own tensors (f.long() of an int32 tensor is a new tensor every time)
         self.textures = textures
         self.device = self._verts[0].device if self._verts else torch.device("cpu")
 

@@ -341,7 +341,94 @@ def uninstall_row_gathers(sugar_model_module):
         delattr(cls, "_sugar_amd_row_gather_original")
 
 
+# ------------------------------------------------------------------------------------------ the mesh binding (refine stage)
+BINDING_PROPERTIES = ("points", "scaling", "quaternions")
+
+
+class _BindingProperty(property):
+    """a property installed by `install_binding`; `original` is the property it replaced"""
+    original = None
+
+
+def _binding_applies(self, name, module) -> bool:
+    """the case csrc/mesh_bind.hip implements: a model bound to a surface mesh, on a ROCm device, not editable, the current
+    (not the paper's old) method, float32 parameters, and -- for `scaling` -- exp as the scale activation"""
+    if not getattr(self, "binded_to_surface_mesh", False) or getattr(self, "editable", False):
+        return False
+    if getattr(module, "use_old_method", False):
+        return False
+    tensors = [self._points, self._surface_mesh_faces] if name != "scaling" else [self._scales]
+    if name == "quaternions":
+        tensors.append(self._quaternions)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        return False
+    floats = [self._scales] if name == "scaling" else [self._points] + ([self._quaternions] if name == "quaternions" else [])
+    if not all(t.dtype == torch.float32 for t in floats):      # the kernels are float32: any other model keeps the reference's dtype
+        return False
+    if name == "scaling":
+        return self.scale_activation is torch.exp and torch.is_tensor(self.surface_mesh_thickness) and self.surface_mesh_thickness.is_cuda
+    return True
+
+
+def _binding_value(self, name):
+    from . import mesh_bind
+    if name == "points":                                                        # sugar_model.py:392-398
+        return mesh_bind.bound_points(self._points, self._surface_mesh_faces, self.surface_triangle_bary_coords)
+    if name == "scaling":                                                       # :420, :438-441
+        return mesh_bind.bound_scaling(self._scales, self.surface_mesh_thickness)
+    return mesh_bind.bound_quaternions(self._points, self._surface_mesh_faces, self._quaternions,   # :449-479
+                                       int(self.n_gaussians_per_surface_triangle))
+
+
+def _row_gather_property(prop):
+    from .row_gather import as_row_gather
+    return property(lambda self, _get=prop.fget: as_row_gather(_get(self)), prop.fset, prop.fdel, prop.__doc__)
+
+
+def install_binding(sugar_model_module):
+    """`SuGaR.points` / `.scaling` / `.quaternions` of a model bound to a surface mesh (sugar_model.py:383-479) come from the HIP kernels
+    of csrc/mesh_bind.hip (sugar_amd.mesh_bind): one forward and one backward call per property instead of the reference's chain of
+    tensor operations.  Only the case `_binding_applies` describes is taken over; every other model -- unbound, on the CPU, editable,
+    `use_old_method`, a scale activation other than exp -- gets the reference's own getter.  Composes with `install_row_gathers` in
+    either order (the value is then viewed as a RowGatherTensor as well).  Idempotent; returns the property names."""
+    cls = sugar_model_module.SuGaR
+    rg_saved = cls.__dict__.get("_sugar_amd_row_gather_original", {})
+    for name in BINDING_PROPERTIES:
+        current = cls.__dict__[name]
+        under_rg = name in rg_saved                   # the row gathers wrap this property: go underneath them
+        prop = rg_saved[name] if under_rg else current
+        if isinstance(prop, _BindingProperty):
+            continue
+
+        def getter(self, _name=name, _get=prop.fget, _module=sugar_model_module):
+            if _binding_applies(self, _name, _module):
+                return _binding_value(self, _name)
+            return _get(self)
+        new = _BindingProperty(getter, prop.fset, prop.fdel, prop.__doc__)
+        new.original = prop
+        if under_rg:
+            rg_saved[name] = new
+            setattr(cls, name, _row_gather_property(new))
+        else:
+            setattr(cls, name, new)
+    return list(BINDING_PROPERTIES)
+
+
+def uninstall_binding(sugar_model_module):
+    cls = sugar_model_module.SuGaR
+    rg_saved = cls.__dict__.get("_sugar_amd_row_gather_original", {})
+    for name in BINDING_PROPERTIES:
+        current = cls.__dict__.get(name)
+        if isinstance(current, _BindingProperty):
+            setattr(cls, name, current.original)
+        elif isinstance(rg_saved.get(name), _BindingProperty):   # the row gathers sit on top: keep them, on the original
+            orig = rg_saved[name].original
+            rg_saved[name] = orig
+            setattr(cls, name, _row_gather_property(orig))
+
+
 def uninstall(sugar_model_module):
+    uninstall_binding(sugar_model_module)
     uninstall_row_gathers(sugar_model_module)
     cls = sugar_model_module.SuGaR
     for name, orig in list(cls.__dict__.get("_sugar_amd_original", {}).items()):
