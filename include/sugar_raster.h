@@ -702,6 +702,33 @@ int sgr_normal_consistency_forward(int n_pairs, int V, const float* verts, const
 int sgr_normal_consistency_backward(int n_pairs, int V, const float* verts, const int32_t* pairs, const float* grad_loss,
                                     const int32_t* vert_offsets, const int32_t* vert_items, float* contrib, float* dL_dverts, void* stream);
 
+/* ---- marching cubes over a dense volume: the mesh of the `use_marching_cubes` branch, sugar_extractors/coarse_mesh.py:623-757 ----------
+ * (csrc/marching_cubes.hip; added under ABI version 4, additive).  volume: float32 [nx, ny, nz], contiguous, z fastest (device);
+ * nx, ny, nz > 0 and nx * ny * nz < 2^31, SGR_E_INVALID otherwise (sgr_marching_cubes_scratch_bytes then returns 0).  iso must be finite.
+ * A corner is inside iff its value is finite and >= iso (NaN, +inf and -inf are outside).  Every crossed grid edge carries one vertex at
+ * t = (iso - a) / (b - a) from its outside end (float32; t = 0.5 when the outside end is not finite, or when t is not -- inf / inf, both
+ * differences overflowing; b - a alone overflowing gives t = 0, a vertex on the outside grid point), in INDEX coordinates.  Vertex
+ * ids: the exclusive scan of crossed edges over the owning grid points in linear order, then axis order x, y, z; faces: linear cell
+ * order, then the order of csrc/mc_table.h; wound so that normals point to lower values.  Outputs are bit-identical between runs.
+ * sgr_marching_cubes_count: classifies and scans into scratch (sgr_marching_cubes_scratch_bytes(nx, ny, nz) bytes, 256-byte aligned)
+ *   and writes counts[2] = (n_verts, n_faces) on the DEVICE; no host synchronisation.  The caller reads counts (the one device-to-host
+ *   read of the extraction), allocates, and calls
+ * sgr_marching_cubes_emit with the same volume, iso and scratch: verts[n_verts,3] (float32), faces[n_faces,3] (int64).  n_verts /
+ *   n_faces must be < 2^31 (SGR_E_INVALID otherwise); rows beyond them are never written.
+ * sgr_mesh_vertex_normals: normals[V,3] = the normalised sum of (b - a) x (c - a) over the faces at each vertex, added in the order of
+ *   the vertex -> (face, corner) CSR list vert_offsets[V+1], vert_items[3F] (item = 3 f + corner); 0 for a vertex with no area around it.
+ *   faces[F,3] int64; a face naming a vertex outside [0, V) is skipped.
+ * sgr_grid_points: out[i] = (X[ix], Y[iy], Z[iz]) of the grid point with linear index start + i, i in [0, n): a slab of the
+ *   [nx*ny*nz, 3] point list of meshgrid(X, Y, Z) without the list.  No call synchronises with the host. */
+size_t sgr_marching_cubes_scratch_bytes(int nx, int ny, int nz);
+int sgr_marching_cubes_count(int nx, int ny, int nz, const float* volume, float iso, void* scratch, int64_t* counts, void* stream);
+int sgr_marching_cubes_emit(int nx, int ny, int nz, const float* volume, float iso, const void* scratch, int64_t n_verts, int64_t n_faces,
+                            float* verts, int64_t* faces, void* stream);
+int sgr_mesh_vertex_normals(int V, int64_t F, const float* verts, const int64_t* faces, const int32_t* vert_offsets,
+                            const int32_t* vert_items, float* normals, void* stream);
+int sgr_grid_points(int nx, int ny, int nz, const float* X, const float* Y, const float* Z, int64_t start, int64_t n, float* out,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,11 @@ SIGNATURES = {
     "sgr_normal_consistency_scratch_bytes": (_sz, []),
     "sgr_normal_consistency_forward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sgr_normal_consistency_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_marching_cubes_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sgr_marching_cubes_count": (_i, [_i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    "sgr_marching_cubes_emit": (_i, [_i, _i, _i, _vp, _f, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "sgr_mesh_vertex_normals": (_i, [_i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_grid_points": (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "sgr_rasterize_meshes": (_i64, [_vp, _i64, _i64, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, ALLOC_FN, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -192,3 +192,88 @@ def camera_to_json(cam_id, name, R, T, fov_x, fov_y, width, height):
     W2C = np.linalg.inv(Rt)
     return {"id": cam_id, "img_name": name, "width": width, "height": height, "position": W2C[:3, 3].tolist(),
             "rotation": [x.tolist() for x in W2C[:3, :3]], "fy": fov2focal(fov_y, height), "fx": fov2focal(fov_x, width)}
+
+
+# ---------------------------------------------------------------- triangle meshes
+def _mesh_array(t, dtype):
+    return np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t), dtype=dtype)
+
+
+def save_mesh_ply(path, verts, faces, normals=None, colors=None):
+    """A triangle mesh as binary little-endian PLY, the layout open3d's `write_triangle_mesh(..., write_vertex_colors=True,
+    write_vertex_normals=True)` gives (coarse_mesh.py:755): element vertex with float x y z, float nx ny nz, uchar red green blue;
+    element face with `list uchar int vertex_indices`.  verts[V,3], faces[F,3] (below 2^31), normals[V,3] or None (zeros),
+    colors[V,3] or None (zeros): uint8 as they are, floats as RGB in [0, 1] (clamped, rounded to the nearest of 255 steps)."""
+    v = _mesh_array(verts, "<f4").reshape(-1, 3)
+    f = _mesh_array(faces, np.int64).reshape(-1, 3)
+    V = v.shape[0]
+    if f.size and (f.min() < 0 or f.max() >= max(V, 1) or V == 0):
+        raise ValueError("save_mesh_ply: a face names a vertex outside [0, V)")
+    n = np.zeros((V, 3), "<f4") if normals is None else _mesh_array(normals, "<f4").reshape(-1, 3)
+    if colors is None:
+        c = np.zeros((V, 3), np.uint8)
+    else:
+        c = colors.detach().cpu().numpy() if torch.is_tensor(colors) else np.asarray(colors)
+        if c.dtype != np.uint8:
+            c = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        c = np.ascontiguousarray(c).reshape(-1, 3)
+    if n.shape[0] != V or c.shape[0] != V:
+        raise ValueError("save_mesh_ply: normals and colors must have one row per vertex")
+    vrec = np.empty(V, dtype=[("p", "<f4", 3), ("n", "<f4", 3), ("c", "u1", 3)])
+    vrec["p"], vrec["n"], vrec["c"] = v, n, c
+    frec = np.empty(f.shape[0], dtype=[("k", "u1"), ("i", "<i4", 3)])
+    frec["k"], frec["i"] = 3, f
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % V
+    header += "".join(f"property float {k}\n" for k in ("x", "y", "z", "nx", "ny", "nz"))
+    header += "".join(f"property uchar {k}\n" for k in ("red", "green", "blue"))
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def load_mesh_ply(path, device="cpu"):
+    """What `save_mesh_ply` wrote -> dict(verts[V,3] float32, faces[F,3] int64, normals[V,3] float32, colors[V,3] uint8) on `device`.
+    Reads binary little-endian PLY files with a vertex element of scalar properties (normals / colours optional: zeros when absent)
+    followed by a face element whose only property is a list of three indices per face."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: only binary_little_endian PLY is supported (got {fmt})")
+        if [e[0] for e in elements] != ["vertex", "face"]:
+            raise ValueError(f"{path}: expected a vertex element followed by a face element")
+        (_, V, vprops), (_, F_, fprops) = elements
+        if any(p[0] == "list" for p in vprops):
+            raise ValueError(f"{path}: list property in the vertex element")
+        vdt = np.dtype([(p[1], _PLY_TYPES[p[0]]) for p in vprops])
+        if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][3] not in ("vertex_indices", "vertex_index"):
+            raise ValueError(f"{path}: the face element must hold one list property vertex_indices")
+        fdt = np.dtype([("k", _PLY_TYPES[fprops[0][1]]), ("i", _PLY_TYPES[fprops[0][2]], 3)])
+        vdata = np.frombuffer(f.read(V * vdt.itemsize), dtype=vdt, count=V)
+        fdata = np.frombuffer(f.read(F_ * fdt.itemsize), dtype=fdt, count=F_)
+    if F_ and not (fdata["k"] == 3).all():
+        raise ValueError(f"{path}: only triangles are supported")
+    cols = lambda names, dt: (np.stack([np.asarray(vdata[k], dtype=dt) for k in names], axis=1) if all(k in vdt.names for k in names)
+                              else np.zeros((V, 3), dt))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return dict(verts=t(cols(("x", "y", "z"), np.float32)), faces=t(fdata["i"].astype(np.int64).reshape(-1, 3)),
+                normals=t(cols(("nx", "ny", "nz"), np.float32)), colors=t(cols(("red", "green", "blue"), np.uint8)))

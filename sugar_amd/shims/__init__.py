@@ -8,8 +8,9 @@ package:
                                `ops.estimate_pointcloud_normals`, the quaternion helpers of `transforms` that SuGaR uses, the
                                camera algebra of `renderer.cameras`, the `structures.Meshes` container and the two
                                `loss` mesh regularisers the surface-bound (refine) model needs, texture containers, and
-                               a mesh rasterizer that raises on use -- mesh rasterization / extraction is outside this
-                               package's scope.
+                               the mesh rasterizer over the HIP z-buffer of sugar_amd.mesh_raster.
+`install()` also exposes the `plyfile` and `mcubes` stand-ins of this directory when the real packages are absent (`mcubes`:
+`marching_cubes` over the HIP kernels of sugar_amd.marching_cubes).
 """
 from __future__ import annotations
 
@@ -42,8 +43,10 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
     the stand-in `pytorch3d.loss.mesh_normal_consistency` of a single mesh run on the HIP kernels of sugar_amd.mesh_bind
     (install_binding); pass the module like `patch_sugar`, or True."""
     real_plyfile = _real_package("plyfile")  # (probed BEFORE the stand-in directory can shadow it on sys.path)
+    real_mcubes = _real_package("mcubes")
     mode = _install_pytorch3d()
     _install_plyfile(real_plyfile)
+    _install_mcubes(real_mcubes)
     if patch_losses:
         install_losses()
     if patch_optimizer:
@@ -331,6 +334,24 @@ def _install_plyfile(real_spec=None) -> None:
             real_spec.loader.exec_module(mod)
         return
     if "plyfile" in sys.modules:
+        return
+    if _HERE not in sys.path:
+        sys.path.insert(0, _HERE)
+    importlib.invalidate_caches()
+
+
+def _install_mcubes(real_spec=None) -> None:
+    """`mcubes` (PyMCubes; coarse_mesh.py:625, the `use_marching_cubes` branch) is not in the ROCm image: when no real package exists,
+    the stand-in under this directory -- `marching_cubes(volume, isovalue)` over the HIP kernels of sugar_amd.marching_cubes -- takes
+    the name.  A real `mcubes` always wins, exactly as for `plyfile`."""
+    if real_spec is not None:
+        mod = sys.modules.get("mcubes")
+        if mod is None or os.path.abspath(getattr(mod, "__file__", "") or "").startswith(_HERE):
+            mod = importlib.util.module_from_spec(real_spec)
+            sys.modules["mcubes"] = mod
+            real_spec.loader.exec_module(mod)
+        return
+    if "mcubes" in sys.modules:
         return
     if _HERE not in sys.path:
         sys.path.insert(0, _HERE)
