@@ -729,6 +729,56 @@ int sgr_mesh_vertex_normals(int V, int64_t F, const float* verts, const int64_t*
 int sgr_grid_points(int nx, int ny, int nz, const float* X, const float* Y, const float* Z, int64_t start, int64_t n, float* out,
                     void* stream);
 
+/* ---- quadric-error mesh decimation and the mesh cleaning passes (csrc/mesh_decimate.hip; added under ABI version 4, additive) ---------
+ * What the reference does with open3d between extraction and refinement (sugar_extractors/coarse_mesh.py:586-605, :722-742).  The rules
+ * -- quadrics, the cost and position of an edge, validity, the per-round independent set, the cleaning rules -- are stated in full at
+ * the top of csrc/mesh_decimate.hip; sugar_amd/decimate.py drives the rounds.  All arithmetic is float64 in a fixed order, integer
+ * atomics only: results are bit-identical between runs.  V, F > 0 and 3 F < 2^31 (SGR_E_INVALID otherwise).  Vertex ids in faces must lie
+ * in [0, V).  P[V,3] float64: coordinates relative to the bounding-box centre; Q[V,10] float64: the vertex quadrics; faces[F,3] int32.
+ * Edge arrays have 3 F entries (one per incidence; the first n_edges are used), indexed by edge id.
+ * sgr_mesh_decimate_edges: from the incidences (3 f + k: edge k of face f, opposite corner k) sorted by (lo * V + hi, incidence) --
+ *   sorted_keys, sorted_incidence, sorted_edge (the edge id of every sorted position) -- the edge records: ends lo < hi, the first two
+ *   faces, the face count capped at 3; boundary_flag[3F] (per incidence) and vert_boundary[V] are set for one-face edges (zero on entry).
+ * sgr_mesh_decimate_quadrics: Q from the faces, the vertex -> (face, corner) CSR list and boundary_flag.
+ * sgr_mesh_decimate_eval: edge_key[3F] (ordered int64 cost bits; the caller fills it with INT64_MAX = invalid) and edge_pos[3F,3] of
+ *   every edge e <= last_edge[0] (a device scalar: the last entry of sorted_edge).
+ * sgr_mesh_decimate_select: edge_order[3F] = the stable argsort of edge_key, n_valid (device scalar) the number of valid keys.  The
+ *   ceil(n_valid / 4) lowest ranks claim their vertices in claim[V] (scratch) with integer atomicMin, in SGR_MESH_DECIMATE_PASSES
+ *   passes; lock[V], dead[3F] and win[3F] are zero on entry; win[r] = the faces removed by the rank-r edge if it won a pass, else 0.
+ * sgr_mesh_decimate_apply: the collapses of the ranks with keep[r] != 0: P, Q, faces (renamed in place), rename[V] (identity on entry),
+ *   vert_keep[V] (ones on entry), face_keep[F] (written).
+ * sgr_mesh_decimate_compact: rows with a keep flag move to (inclusive scan - 1); faces are renumbered through vert_pos.  P / Q / verts
+ *   (float32) may each be NULL.
+ * sgr_mesh_clean_*: flags of the cleaning rules (degenerate: a repeated index; duplicate faces: perm orders faces by (sorted vertex
+ *   triple, id), all but the first of a run are dropped; duplicate vertices: perm orders vertices by (coordinate bits, id), run_start[i]
+ *   = 1 where a run of bit-equal vertices begins; non-manifold: every edge with more than two faces marks its smallest face, ties to the
+ *   highest id; referenced: vert_referenced[v] = 1 for every vertex a face names).  No call synchronises with the host. */
+#define SGR_MESH_DECIMATE_PASSES 4
+int sgr_mesh_decimate_quadrics(int V, int F, const double* P, const int32_t* faces, const int32_t* vert_offsets, const int32_t* vert_items,
+                               const uint8_t* boundary_flag, double boundary_weight, double* Q, void* stream);
+int sgr_mesh_decimate_edges(int V, int F, const int64_t* sorted_keys, const int64_t* sorted_incidence, const int64_t* sorted_edge,
+                            int32_t* e_lo, int32_t* e_hi, int32_t* e_f0, int32_t* e_f1, int32_t* e_nf, uint8_t* boundary_flag,
+                            int32_t* vert_boundary, void* stream);
+int sgr_mesh_decimate_eval(int V, int F, const int64_t* last_edge, const double* P, const double* Q, const int32_t* faces,
+                           const int32_t* vert_offsets, const int32_t* vert_items, const int32_t* e_lo, const int32_t* e_hi,
+                           const int32_t* e_f0, const int32_t* e_f1, const int32_t* e_nf, const int32_t* vert_boundary, int64_t* edge_key,
+                           double* edge_pos, void* stream);
+int sgr_mesh_decimate_select(int V, int F, const int64_t* n_valid, const int64_t* edge_order, const int32_t* e_lo, const int32_t* e_hi,
+                             const int32_t* e_nf, const int32_t* faces, const int32_t* vert_offsets, const int32_t* vert_items,
+                             int64_t* claim, int32_t* lock, uint8_t* dead, int32_t* win, void* stream);
+int sgr_mesh_decimate_apply(int V, int F, const uint8_t* keep, const int64_t* edge_order, const int32_t* e_lo, const int32_t* e_hi,
+                            const double* edge_pos, double* P, double* Q, int32_t* faces, int32_t* rename, int32_t* vert_keep,
+                            int32_t* face_keep, void* stream);
+int sgr_mesh_decimate_compact(int V, int F, const int32_t* vert_keep, const int64_t* vert_pos, const int32_t* face_keep, const int64_t* face_pos,
+                              const double* P, const double* Q, const float* verts, const int32_t* faces, double* P_out, double* Q_out,
+                              float* verts_out, int32_t* faces_out, void* stream);
+int sgr_mesh_clean_degenerate(int F, const int32_t* faces, int32_t* face_keep, void* stream);
+int sgr_mesh_clean_duplicate_faces(int F, const int32_t* faces, const int64_t* perm, int32_t* face_keep, void* stream);
+int sgr_mesh_clean_duplicate_verts(int V, const float* verts, const int64_t* perm, int64_t* run_start, void* stream);
+int sgr_mesh_clean_nonmanifold(int V, int F, const int64_t* sorted_keys, const int64_t* sorted_incidence, const float* verts,
+                               const int32_t* faces, int32_t* face_remove, void* stream);
+int sgr_mesh_clean_referenced(int V, int F, const int32_t* faces, int32_t* vert_referenced, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

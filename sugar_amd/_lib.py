@@ -112,6 +112,17 @@ SIGNATURES = {
     "sgr_marching_cubes_emit": (_i, [_i, _i, _i, _vp, _f, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sgr_mesh_vertex_normals": (_i, [_i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgr_grid_points": (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "sgr_mesh_decimate_quadrics": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "sgr_mesh_decimate_edges": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_decimate_eval": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_decimate_select": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_decimate_apply": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_decimate_compact": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_clean_degenerate": (_i, [_i, _vp, _vp, _vp]),
+    "sgr_mesh_clean_duplicate_faces": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_clean_duplicate_verts": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_clean_nonmanifold": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_mesh_clean_referenced": (_i, [_i, _i, _vp, _vp, _vp]),
     "sgr_rasterize_meshes": (_i64, [_vp, _i64, _i64, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, ALLOC_FN, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -30,6 +30,7 @@ SOURCES = {
     "texture.hip": ["-ffp-contract=off"],      # the texel arithmetic of the reference's individually rounded tensor ops
     "mesh_bind.hip": ["-ffp-contract=off"],    # the binding restates the reference's individually rounded tensor arithmetic
     "marching_cubes.hip": ["-ffp-contract=off"],  # bit-identical with the serial restatement in tests/mc_restatement.py
+    "mesh_decimate.hip": ["-ffp-contract=off"],   # bit-identical with the serial restatement in tests/decimate_restatement.py
     "loss.hip": [],
     "adam.hip": [],
     "activations.hip": [],

@@ -1,5 +1,5 @@
 """Coarse mesh extraction by marching cubes, on the device from the Gaussians to the mesh: the `use_marching_cubes` branch of
-sugar_extractors/coarse_mesh.py (:623-757) up to, and not including, its open3d calls.
+sugar_extractors/coarse_mesh.py (:623-757); its open3d calls (decimation, cleaning) are sugar_amd.decimate's, on request.
 
   density_grid(X, Y, Z, centers, inv_scaled_rot, strengths, ...)  -> volume[nx,ny,nz]: `SuGaR.compute_density` (sugar_model.py:1345-1368)
       on the grid meshgrid(X, Y, Z), swept in slabs: sgr_grid_points writes a slab's points, the HIP k-NN finds each point's K nearest
@@ -13,10 +13,13 @@ Deliberate differences from the reference:
   * vertices sit at the true grid coordinates X[i] + t (X[i+1] - X[i]).  The reference maps index coordinates with
     `-extent + vertices / resolution * 2 extent` (:661) although linspace(-1, 1, resolution) has a spacing of 2 / (resolution - 1): its
     vertices are off by up to one cell at the far end of each axis;
-  * no decimation and no cleaning passes: `simplify_quadric_decimation` and the `remove_*` calls (:716-742) are open3d's.  The mesh
-    returned here is the full marching-cubes mesh.
+  * decimation and cleaning are opt-in: by default the mesh returned here is the full marching-cubes mesh.  With `decimation_target=N`
+    the foreground and the background mesh are each decimated to N faces by sugar_amd.decimate.decimate, and with `clean=True` each is
+    then cleaned by sugar_amd.decimate.clean -- `simplify_quadric_decimation` and the `remove_*` calls of :716-742, as native HIP code
+    with its own stated rules (not open3d's implementation).  Normals and colours are computed after both.
 
     python -m sugar_amd.extract point_cloud.ply --out mesh.ply [--resolution 512 --level 0.3 --extent E --no-background]
+                                                               [--decimate N [--no-clean]]
 
 There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
@@ -27,6 +30,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import decimate as _decimate
 from . import field as _field
 from . import marching_cubes as _mc
 from .knn import knn_points
@@ -114,23 +118,30 @@ def nearest_gaussian_colors(verts, points, sh_dc):
     return 0.5 + SH_C0 * sh_dc.reshape(-1, 3)[idx], idx
 
 
-def _one_mesh(X, centers, B, strengths, sh_dc, level, K, points_per_pass, zero_inside):
+def _one_mesh(X, centers, B, strengths, sh_dc, level, K, points_per_pass, zero_inside, decimation_target=None, clean=False):
     volume = density_grid(X, X, X, centers, B, strengths, K=K, points_per_pass=points_per_pass, zero_inside=zero_inside)
     verts_index, faces = _mc.marching_cubes(volume, level)
     del volume
     verts = grid_to_world(verts_index, X, X, X)
+    if decimation_target is not None and faces.shape[0]:
+        verts, faces, _ = _decimate.decimate(verts, faces, int(decimation_target))
+    if clean and faces.shape[0]:
+        verts, faces, _ = _decimate.clean(verts, faces)
     colors, _ = nearest_gaussian_colors(verts, centers, sh_dc)
     normals = _mc.vertex_normals(verts, faces) if verts.shape[0] else verts.new_zeros(0, 3)
     return verts, faces, normals, colors
 
 
 def extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, extent, resolution: int = 512, level: float = 0.3,
-                                background: bool = True, K: int = 16, points_per_pass: int = 2_000_000):
+                                background: bool = True, K: int = 16, points_per_pass: int = 2_000_000, decimation_target=None,
+                                clean: bool = False):
     """The marching-cubes mesh of a coarse SuGaR model.  points[P,3]; scales[P,3] (activated: `SuGaR.scaling`); quaternions[P,4] (real
     part first); opacities[P] or [P,1] in [0, 1] (`SuGaR.strengths`); sh_dc[P,3] or [P,1,3] (`_sh_coordinates_dc`); extent: the cameras'
     spatial extent (`get_cameras_spatial_extent()`); level: surface_levels[0].
     Returns dict(verts[V,3] float32, faces[F,3] int64, normals[V,3], colors[V,3] in RGB floats (0.5 + C0 dc, not clamped)), the foreground
-    mesh first, then (background=True) the background mesh.  See the module docstring for the differences from the reference."""
+    mesh first, then (background=True) the background mesh.  decimation_target=N: each of the two meshes is decimated to at most N faces
+    (coarse_mesh.py:722-727); clean=True: each is then cleaned (:734-742).  With the defaults neither happens and the output is the full
+    marching-cubes mesh.  See the module docstring for the differences from the reference."""
     if not torch.is_tensor(points) or not points.is_cuda:
         raise RuntimeError("extract_mesh_marching_cubes: points must be a tensor on a ROCm device; there is no CPU fallback")
     dev = points.device
@@ -145,9 +156,12 @@ def extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, e
     strengths = opacities.detach().float().reshape(-1)
     dc = sh_dc.detach().float().reshape(-1, 3)
     lin = torch.linspace(-1, 1, resolution, device=dev)
-    parts = [_one_mesh(lin * extent, centers, B, strengths, dc, level, K, points_per_pass, None)]
+    if decimation_target is not None and int(decimation_target) < 0:
+        raise ValueError("extract_mesh_marching_cubes: decimation_target must not be negative")
+    post = (decimation_target, bool(clean))
+    parts = [_one_mesh(lin * extent, centers, B, strengths, dc, level, K, points_per_pass, None, *post)]
     if background:
-        parts.append(_one_mesh(lin * BACKGROUND_SCALE * extent, centers, B, strengths, dc, level, K, points_per_pass, (-extent, extent)))
+        parts.append(_one_mesh(lin * BACKGROUND_SCALE * extent, centers, B, strengths, dc, level, K, points_per_pass, (-extent, extent), *post))
     n_fg = parts[0][0].shape[0]
     verts = torch.cat([m[0] for m in parts])
     faces = torch.cat([m[1] + (n_fg if i else 0) for i, m in enumerate(parts)])
@@ -164,6 +178,9 @@ def main(argv=None):
     ap.add_argument("--extent", type=float, default=None,
                     help="half-size of the foreground grid (the cameras' spatial extent); default: the 99th percentile of max(|x|, |y|, |z|)")
     ap.add_argument("--no-background", action="store_true")
+    ap.add_argument("--decimate", type=int, default=None, metavar="N",
+                    help="decimate the foreground and the background mesh to at most N faces each, then clean them")
+    ap.add_argument("--no-clean", action="store_true", help="with --decimate: skip the cleaning passes")
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args(argv)
     g = io.load_gaussian_ply(a.point_cloud, device=a.device)
@@ -172,7 +189,8 @@ def main(argv=None):
         r = g["xyz"].abs().max(dim=1).values
         extent = float(r.kthvalue(max(1, int(0.99 * r.numel()))).values)
     mesh = extract_mesh_marching_cubes(g["xyz"], torch.exp(g["scaling"]), g["rotation"], torch.sigmoid(g["opacity"]), g["features"][:, 0, :],
-                                       extent, resolution=a.resolution, level=a.level, background=not a.no_background)
+                                       extent, resolution=a.resolution, level=a.level, background=not a.no_background,
+                                       decimation_target=a.decimate, clean=a.decimate is not None and not a.no_clean)
     io.save_mesh_ply(a.out, mesh["verts"], mesh["faces"], normals=mesh["normals"], colors=mesh["colors"])
     print(f"{a.out}: {mesh['verts'].shape[0]} vertices, {mesh['faces'].shape[0]} faces (extent {extent:.4g}, level {a.level})")
     return 0
