@@ -74,7 +74,7 @@ def sweep_split(X, pts, B, st, K=16, ppp=2_000_000):
     packed = field._pack(lib, pts, B.reshape(-1, 9).contiguous(), st)
     buf = torch.empty(min(ppp, N), 3, device=DEV); opac = torch.empty(min(ppp, N), K, device=DEV); dens = torch.empty(min(ppp, N), device=DEV)
     stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    p = field._p
+    from sugar_amd._call import ptr as p
     Bm = B.reshape(-1, 9).contiguous()
     ev = []
     for start in range(0, N, ppp):

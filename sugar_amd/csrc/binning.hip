@@ -65,18 +65,6 @@ __device__ __forceinline__ uint32_t rs_digit(uint32_t key, uint32_t kmin, uint32
     return (((key == 0xFFFFFFFFu ? kmax1 : key) - kmin) >> shift) & 255u;
 }
 
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += y;
-    }
-    return v;
-}
-
 // Chained scan ("decoupled look-back") state of a pass: one word per (chunk, digit), zero = nothing published yet,
 // otherwise the count in the low 30 bits and one of two flags: A = this chunk's own count, P = the inclusive sum over this
 // chunk and all chunks before it.  Value and flag share a word, so relaxed agent-scope loads and stores are enough.
@@ -232,7 +220,7 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_pass(int n, const uint32_t* _
         tot = counters[pass * 256 + tid];
         // two exclusive scans over the 256 digits: the chunk's counts (chunk-local starts) and the global totals (run
         // starts): shuffle scans inside the four waves, then the earlier waves' totals (one barrier instead of 32)
-        i_mine = wave_incl_scan(mine); i_tot = wave_incl_scan(tot);
+        i_mine = sgr_wave_incl_scan(mine); i_tot = sgr_wave_incl_scan(tot);
         if (lane == 63) { s_scan[wave] = i_mine; s_scan[4 + wave] = i_tot; }
     }
     __syncthreads();
@@ -456,13 +444,13 @@ __global__ void __launch_bounds__(1024) k_tile_scan(int T, const uint32_t* __res
             if (base + j * 1024 + tid >= T) c[j] = 0u;
             exact += c[j];
             mx = max(mx, c[j]);
-            incl[j] = wave_incl_scan(c[j]);
+            incl[j] = sgr_wave_incl_scan(c[j]);
             if (lane == 63) s_seg[j * 16 + wave] = incl[j];
         }
         __syncthreads();
         if (wave == 0) {  // exclusive scan of the 128 segment totals, two per lane
             const uint32_t a0 = s_seg[2 * lane], a1 = s_seg[2 * lane + 1];
-            const uint32_t p = wave_incl_scan(a0 + a1);
+            const uint32_t p = sgr_wave_incl_scan(a0 + a1);
             s_seg[2 * lane] = p - a0 - a1;
             s_seg[2 * lane + 1] = p - a1;
             if (lane == 63) s_total = p;

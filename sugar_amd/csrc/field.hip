@@ -13,7 +13,7 @@
 //                   One lane per pixel; a_g = B_g^T (p - mu_g) and b_g = B_g^T dir are formed once per neighbour, so a
 //                   sample costs 3 FMAs + |.|^2 + one exp per neighbour instead of a 3x3 product.
 #include "../../include/sugar_raster.h"
-#include "sgr_common.h"
+#include "sgr_device.h"
 
 namespace {
 
@@ -266,14 +266,9 @@ __global__ void __launch_bounds__(256) k_fscan_apply(int n, const uint32_t* __re
     uint32_t v[8], sum = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) { v[i] = (base + i < n) ? cnt[base + i] : 0u; sum += v[i]; }
-    uint32_t incl = sum;
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += y; }
-    if (lane == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t run = block_sums[blockIdx.x] + incl - sum;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) run += s_w[w];
+    uint32_t run;
+    sgr_block_scan<4>(sum, s_w, run);
+    run += block_sums[blockIdx.x];
 #pragma unroll
     for (int i = 0; i < 8; i++) { if (base + i < n) start[base + i] = run; run += v[i]; }
 }

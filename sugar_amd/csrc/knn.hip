@@ -11,7 +11,7 @@
 // a candidate is rejected with a single compare against the current worst.  Squared distances are evaluated as
 // (dx*dx + dy*dy) + dz*dz with individually rounded ops (-ffp-contract=off), identical to the oracle.
 #include "../../include/sugar_raster.h"
-#include "sgr_common.h"
+#include "sgr_device.h"
 #include <cstdlib>
 #include <string>
 
@@ -348,30 +348,6 @@ __device__ __forceinline__ unsigned int grid_scan_load16(int n, const unsigned i
     return sum;
 }
 
-// sum over the 256 threads of a workgroup, returned to every thread; `mine_excl` = sum over the threads before this one
-__device__ __forceinline__ unsigned int grid_block_scan(unsigned int x, unsigned int* s_wave, unsigned int& mine_excl)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned int y = (unsigned int)__shfl_up((int)incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const unsigned int t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    mine_excl = before + incl - x;
-    __syncthreads();
-    return total;
-}
-
 __global__ void __launch_bounds__(256) k_grid_blocksum(int n, const unsigned int* __restrict__ cnt, unsigned int* __restrict__ part,
                                                        GridHdr* __restrict__ hdr)
 {
@@ -385,7 +361,7 @@ __global__ void __launch_bounds__(256) k_grid_blocksum(int n, const unsigned int
     __shared__ unsigned int s_occ[4];
     for (int o = 32; o > 0; o >>= 1) occ += (unsigned int)__shfl_xor((int)occ, o);
     if ((threadIdx.x & 63) == 0) s_occ[threadIdx.x >> 6] = occ;
-    const unsigned int total = grid_block_scan(sum, s_wave, excl);   // (has the workgroup barriers that publish s_occ)
+    const unsigned int total = sgr_block_scan<4>(sum, s_wave, excl);   // (has the workgroup barriers that publish s_occ)
     __syncthreads();
     if (threadIdx.x == 0) {
         part[blockIdx.x] = total;
@@ -400,11 +376,11 @@ __global__ void __launch_bounds__(256) k_grid_scan(int n, const unsigned int* __
     __shared__ unsigned int s_wave[4];
     unsigned int before = 0, excl;
     for (int j = (int)threadIdx.x; j < (int)blockIdx.x; j += 256) before += part[j];
-    const unsigned int offset = grid_block_scan(before, s_wave, excl);
+    const unsigned int offset = sgr_block_scan<4>(before, s_wave, excl);
     unsigned int v[16];
     const int base = (int)blockIdx.x * GRID_SCAN_BLOCK + (int)threadIdx.x * 16;
     const unsigned int sum = grid_scan_load16(n, cnt, base, v);
-    const unsigned int total = grid_block_scan(sum, s_wave, excl);
+    const unsigned int total = sgr_block_scan<4>(sum, s_wave, excl);
     unsigned int run = offset + excl;
     if (base + 16 <= n) {
         unsigned int o[16];
@@ -589,9 +565,7 @@ template <class F>
 __device__ __forceinline__ void visit_rows(const float4* __restrict__ sorted, unsigned int b, unsigned int e, int lane, F&& f)
 {
     const unsigned int cnt = e > b ? e - b : 0u;
-    unsigned int inc = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    const unsigned int inc = sgr_wave_incl_scan(cnt);
     const unsigned int total = __shfl(inc, 63), excl = inc - cnt;
     for (unsigned int base = 0; base < total; base += 64u * VISIT_WIDTH) {
         unsigned int sl[VISIT_WIDTH], at[VISIT_WIDTH];

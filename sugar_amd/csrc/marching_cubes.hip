@@ -25,7 +25,7 @@
 //                    base[owner's group] + (set bits of the group's mask bytes below the owner) + (owned edges below the axis).
 // No kernel communicates with another workgroup inside a launch.
 #include "../../include/sugar_raster.h"
-#include "sgr_common.h"
+#include "sgr_device.h"
 #define MC_TABLE_QUAL static __device__ const
 #include "mc_table.h"
 
@@ -137,19 +137,10 @@ __global__ void __launch_bounds__(MC_SCAN_THREADS) k_mc_group_scan(int64_t G, co
         const uint32_t t = mc_word_tris(c.x, ntri) + mc_word_tris(c.y, ntri) + mc_word_tris(c.z, ntri) + mc_word_tris(c.w, ntri);
         x = v | (t << 16);
     }
-    const int lane = tid & 63, wave = tid >> 6;
-    uint32_t inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    if (g < G) grp[g] = base + inc - x;
-    if (tid == MC_SCAN_THREADS - 1) blk[blockIdx.x] = base + inc;
+    uint32_t before;
+    const uint32_t total = sgr_block_scan<MC_SCAN_THREADS / 64>(x, wave_tot, before);
+    if (g < G) grp[g] = before;
+    if (tid == 0) blk[blockIdx.x] = total;
 }
 
 // blk[NB] packed totals -> blk_v[NB], blk_t[NB]: exclusive offsets (low 32 bits; the caller refuses totals >= 2^31), counts[2] = totals

@@ -17,7 +17,7 @@
 // and, behind the level-set kernel, sgr_compact_level_rows gathers every level's valid rows to the front of fixed-size outputs and
 // leaves the per-level counts on the device.
 #include "../../include/sugar_raster.h"
-#include "sgr_common.h"
+#include "sgr_device.h"
 
 namespace {
 
@@ -86,15 +86,9 @@ __global__ void __launch_bounds__(1024) k_pick_select(const uint32_t* __restrict
     constexpr int PER = PICK_BINS / 1024;
     uint32_t sum = 0;
     for (int j = 0; j < PER; j++) sum += hist[tid * PER + j];
-    uint32_t incl = sum;
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d); if (lane >= d) incl += y; }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wave; w++) before += s_wave[w];
-    incl += before;
-    const uint32_t excl = incl - sum;
+    uint32_t excl;
+    sgr_block_scan<16>(sum, s_wave, excl);
+    const uint32_t incl = excl + sum;
     if (excl < need && need <= incl) {   // the crossing lies in this thread's bins (exactly one thread)
         uint32_t run = excl;
         for (int j = 0; j < PER; j++) {
@@ -137,23 +131,15 @@ __global__ void __launch_bounds__(PICK_BLOCK) k_pick_count(int n, const float* _
 __global__ void __launch_bounds__(1024) k_pick_scan(int n_blocks, uint32_t* __restrict__ blk_count)
 {
     __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0u;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    uint32_t carry = 0u;   // the sum of the rounds before this one: every thread holds it
     for (int base = 0; base < n_blocks; base += 1024) {
         const int i = base + tid;
         const uint32_t v = i < n_blocks ? blk_count[i] : 0u;
-        uint32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)incl, d); if (lane >= d) incl += y; }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (int w = 0; w < wave; w++) before += s_wave[w];
-        if (i < n_blocks) blk_count[i] = before + incl - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = before + incl;
-        __syncthreads();
+        uint32_t excl;
+        const uint32_t total = sgr_block_scan<16>(v, s_wave, excl);
+        if (i < n_blocks) blk_count[i] = carry + excl;
+        carry += total;
     }
 }
 

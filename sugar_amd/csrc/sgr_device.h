@@ -1,6 +1,40 @@
-// sgr_device.h -- device helpers shared by preprocess.hip and binning.hip.
+// sgr_device.h -- device helpers shared by the translation units: the tile rectangle of preprocess.hip and binning.hip, and the
+// wave and workgroup prefix sums of every kernel that forms one (binning, k-NN grid, field scatter, pixel pick, marching cubes).
 #pragma once
 #include "sgr_common.h"
+
+// inclusive scan over the 64 lanes of a wave
+__device__ __forceinline__ uint32_t sgr_wave_incl_scan(uint32_t v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v += y;
+    }
+    return v;
+}
+
+// sum of x over the WAVES * 64 threads of a workgroup, returned to every thread; `excl` = the sum over the threads before this one.
+// Every thread of the workgroup must call it (two barriers; s_wave[WAVES] may be reused after it returns).
+template <int WAVES>
+__device__ __forceinline__ uint32_t sgr_block_scan(uint32_t x, uint32_t* s_wave, uint32_t& excl)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t incl = sgr_wave_incl_scan(x);
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+        const uint32_t t = s_wave[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    excl = before + incl - x;
+    __syncthreads();
+    return total;
+}
 
 __device__ __forceinline__ int sgr_f2i_sat(float v)
 {

@@ -6,7 +6,7 @@
 // workgroup of the loss forward kernel, which is what follows the blend in the train step: the 12 us of this serial,
 // single-workgroup job leave the step's chain).
 #pragma once
-#include "sgr_common.h"
+#include "sgr_device.h"
 
 struct SgrTileOrderJob {
     int T;                       // tiles; 0 = no job
@@ -134,12 +134,7 @@ __device__ __forceinline__ void sgr_tile_order_block(const SgrTileOrderJob& j)
     uint32_t loc[CPT], mine = 0;
 #pragma unroll
     for (int k = 0; k < CPT; k++) { loc[k] = s_cls[tid * CPT + k]; mine += loc[k]; }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, d);
-        if (lane >= d) incl += y;
-    }
+    const uint32_t incl = sgr_wave_incl_scan(mine);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     uint32_t run = incl - mine;

@@ -19,32 +19,11 @@ ONE device-to-host read per round -- `counts.tolist()` in `_round`, the triple (
 `clean` reads one count per pass (and one per round of the non-manifold rule).  There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
+from ._call import call, csr, need_gpu, ptr
 
 KEY_INVALID = 2 ** 63 - 1
-
-
-def _vp(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check(rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name} failed ({rc}): {_lib.last_error()}")
-
-
-def _need_gpu(what, **tensors):
-    for name, t in tensors.items():
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a tensor on a ROCm device; there is no CPU fallback")
 
 
 def _shapes(what, verts, faces):
@@ -73,17 +52,10 @@ def _sorted_incidences(faces32, V):
     return torch.sort(key, stable=True)
 
 
-def _vertex_csr(faces32, V):
-    """the vertex -> (face, corner) list as sugar_amd.marching_cubes.vertex_normals builds it (no host read)"""
-    sorted_flat, items = torch.sort(faces32.reshape(-1).to(torch.int64), stable=True)
-    offsets = torch.searchsorted(sorted_flat, torch.arange(V + 1, device=faces32.device))
-    return offsets.to(torch.int32), items.to(torch.int32)
-
-
 class _Edges:
     """the edge records of one faces tensor (every array has 3 F entries; the first n_edges are used)"""
 
-    def __init__(self, lib, faces32, V):
+    def __init__(self, faces32, V):
         dev = faces32.device
         F_ = int(faces32.shape[0])
         n = 3 * F_
@@ -96,36 +68,29 @@ class _Edges:
         self.lo, self.hi, self.f0, self.f1, self.nf = i32(), i32(), i32(), i32(), i32()
         self.bflag = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.vbnd = torch.zeros(V, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_mesh_decimate_edges(V, F_, _vp(skey), _vp(order), _vp(group), _vp(self.lo), _vp(self.hi), _vp(self.f0),
-                                             _vp(self.f1), _vp(self.nf), _vp(self.bflag), _vp(self.vbnd), _stream(dev))
-        _check(rc, "sgr_mesh_decimate_edges")
+        call("sgr_mesh_decimate_edges", dev, V, F_, ptr(skey), ptr(order), ptr(group), ptr(self.lo), ptr(self.hi), ptr(self.f0),
+             ptr(self.f1), ptr(self.nf), ptr(self.bflag), ptr(self.vbnd))
 
 
-def _round(lib, P, Q, faces32, target):
+def _round(P, Q, faces32, target):
     """one round of collapses; returns (P, Q, faces, n_collapsed).  The one host read of the round is `counts.tolist()`."""
     dev = P.device
     V, F_ = int(P.shape[0]), int(faces32.shape[0])
     n = 3 * F_
-    st = _stream(dev)
-    ed = _Edges(lib, faces32, V)
-    offsets, items = _vertex_csr(faces32, V)
+    ed = _Edges(faces32, V)
+    offsets, items = csr(faces32, V)
     ekey = torch.full((n,), KEY_INVALID, dtype=torch.int64, device=dev)
     epos = torch.empty(n, 3, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_eval(V, F_, _vp(ed.last_edge), _vp(P), _vp(Q), _vp(faces32), _vp(offsets), _vp(items), _vp(ed.lo),
-                                        _vp(ed.hi), _vp(ed.f0), _vp(ed.f1), _vp(ed.nf), _vp(ed.vbnd), _vp(ekey), _vp(epos), st)
-    _check(rc, "sgr_mesh_decimate_eval")
+    call("sgr_mesh_decimate_eval", dev, V, F_, ptr(ed.last_edge), ptr(P), ptr(Q), ptr(faces32), ptr(offsets), ptr(items), ptr(ed.lo),
+         ptr(ed.hi), ptr(ed.f0), ptr(ed.f1), ptr(ed.nf), ptr(ed.vbnd), ptr(ekey), ptr(epos))
     order_e = torch.sort(ekey, stable=True).indices
     n_valid = (ekey != KEY_INVALID).sum().reshape(1)
     claim = torch.empty(V, dtype=torch.int64, device=dev)
     lock = torch.zeros(V, dtype=torch.int32, device=dev)
     dead = torch.zeros(n, dtype=torch.uint8, device=dev)
     win = torch.zeros(n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_select(V, F_, _vp(n_valid), _vp(order_e), _vp(ed.lo), _vp(ed.hi), _vp(ed.nf), _vp(faces32), _vp(offsets),
-                                          _vp(items), _vp(claim), _vp(lock), _vp(dead), _vp(win), st)
-    _check(rc, "sgr_mesh_decimate_select")
+    call("sgr_mesh_decimate_select", dev, V, F_, ptr(n_valid), ptr(order_e), ptr(ed.lo), ptr(ed.hi), ptr(ed.nf), ptr(faces32), ptr(offsets),
+         ptr(items), ptr(claim), ptr(lock), ptr(dead), ptr(win))
     removed = win.to(torch.int64)
     before = torch.cumsum(removed, 0) - removed             # faces removed by the winners of lower rank
     keep = (win > 0) & ((F_ - before) > int(target))
@@ -133,16 +98,12 @@ def _round(lib, P, Q, faces32, target):
     rename = torch.arange(V, dtype=torch.int32, device=dev)
     vkeep = torch.ones(V, dtype=torch.int32, device=dev)
     fkeep = torch.empty(F_, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_apply(V, F_, _vp(keep8), _vp(order_e), _vp(ed.lo), _vp(ed.hi), _vp(epos), _vp(P), _vp(Q), _vp(faces32),
-                                         _vp(rename), _vp(vkeep), _vp(fkeep), st)
-    _check(rc, "sgr_mesh_decimate_apply")
+    call("sgr_mesh_decimate_apply", dev, V, F_, ptr(keep8), ptr(order_e), ptr(ed.lo), ptr(ed.hi), ptr(epos), ptr(P), ptr(Q), ptr(faces32),
+         ptr(rename), ptr(vkeep), ptr(fkeep))
     vpos, fpos = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
     P2, Q2, faces2 = torch.empty_like(P), torch.empty_like(Q), torch.empty_like(faces32)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_compact(V, F_, _vp(vkeep), _vp(vpos), _vp(fkeep), _vp(fpos), _vp(P), _vp(Q), None, _vp(faces32), _vp(P2),
-                                           _vp(Q2), None, _vp(faces2), st)
-    _check(rc, "sgr_mesh_decimate_compact")
+    call("sgr_mesh_decimate_compact", dev, V, F_, ptr(vkeep), ptr(vpos), ptr(fkeep), ptr(fpos), ptr(P), ptr(Q), None, ptr(faces32), ptr(P2),
+         ptr(Q2), None, ptr(faces2))
     counts = torch.stack([vpos[-1], fpos[-1], keep.sum()])
     n_verts, n_faces, n_collapsed = counts.tolist()          # the one device-to-host read of the round
     return P2[:n_verts], Q2[:n_verts], faces2[:n_faces], n_collapsed
@@ -153,7 +114,7 @@ def decimate(verts: torch.Tensor, faces: torch.Tensor, target_faces: int, bounda
     int32 / int64 on a ROCm device; the mesh should be clean (see `clean`): faces with a repeated index and edges with more than two
     faces are never collapsed.  Returns (verts float32, faces int64, info) with info = dict(rounds, faces, target, target_met,
     round_limit).  A target of at least F returns the input (as float32 / int64) unchanged."""
-    _need_gpu("decimate", verts=verts, faces=faces)
+    need_gpu("decimate", verts=verts, faces=faces)
     _shapes("decimate", verts, faces)
     target = int(target_faces)
     if target < 0:
@@ -167,22 +128,19 @@ def decimate(verts: torch.Tensor, faces: torch.Tensor, target_faces: int, bounda
         return v32, f64, info
     if bool(((f64 < 0) | (f64 >= V)).any()):                 # the read before the first round
         raise ValueError(f"decimate: a face names a vertex outside [0, {V})")
-    lib = _lib.load()
     dev = v32.device
     faces32 = f64.to(torch.int32)
     centre = 0.5 * (v32.min(dim=0).values.to(torch.float64) + v32.max(dim=0).values.to(torch.float64))
     P = (v32.to(torch.float64) - centre).contiguous()
-    ed = _Edges(lib, faces32, V)
-    offsets, items = _vertex_csr(faces32, V)
+    ed = _Edges(faces32, V)
+    offsets, items = csr(faces32, V)
     Q = torch.empty(V, 10, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_quadrics(V, F_, _vp(P), _vp(faces32), _vp(offsets), _vp(items), _vp(ed.bflag), float(boundary_weight),
-                                            _vp(Q), _stream(dev))
-    _check(rc, "sgr_mesh_decimate_quadrics")
+    call("sgr_mesh_decimate_quadrics", dev, V, F_, ptr(P), ptr(faces32), ptr(offsets), ptr(items), ptr(ed.bflag), float(boundary_weight),
+         ptr(Q))
     del ed, offsets, items
     rounds = 0
     while faces32.shape[0] > target and rounds < limit:
-        P, Q, faces32, n_collapsed = _round(lib, P, Q, faces32, target)
+        P, Q, faces32, n_collapsed = _round(P, Q, faces32, target)
         rounds += 1
         if n_collapsed == 0 or faces32.shape[0] == 0:
             break
@@ -210,14 +168,12 @@ def clean(verts: torch.Tensor, faces: torch.Tensor, degenerate: bool = True, dup
                             (|(b - a) x (c - a)|^2 in float64; ties to the highest face id), in rounds;
     then vertices that no face names are removed (always).  Faces and vertices keep their relative order.
     Returns (verts float32, faces int64, vertex_map int64[V])."""
-    _need_gpu("clean", verts=verts, faces=faces)
+    need_gpu("clean", verts=verts, faces=faces)
     _shapes("clean", verts, faces)
-    lib = _lib.load()
     v = verts.detach().to(torch.float32).contiguous()
     f = faces.detach().to(torch.int32).contiguous()
     dev = v.device
     V = int(v.shape[0])
-    st = lambda: _stream(dev)
     vmap = torch.arange(V, dtype=torch.int64, device=dev)
     if V and f.shape[0] and bool(((f < 0) | (f >= V)).any()):
         raise ValueError(f"clean: a face names a vertex outside [0, {V})")
@@ -227,20 +183,17 @@ def clean(verts: torch.Tensor, faces: torch.Tensor, degenerate: bool = True, dup
 
     if degenerate and f.shape[0]:
         keep = ones(f.shape[0])
-        with torch.cuda.device(dev):
-            _check(lib.sgr_mesh_clean_degenerate(int(f.shape[0]), _vp(f), _vp(keep), st()), "sgr_mesh_clean_degenerate")
+        call("sgr_mesh_clean_degenerate", dev, int(f.shape[0]), ptr(f), ptr(keep))
         f = f[keep.bool()].contiguous()
     if duplicated_triangles and f.shape[0]:
         perm = _lexsort_rows(torch.sort(f, dim=1).values)
         keep = ones(f.shape[0])
-        with torch.cuda.device(dev):
-            _check(lib.sgr_mesh_clean_duplicate_faces(int(f.shape[0]), _vp(f), _vp(perm), _vp(keep), st()), "sgr_mesh_clean_duplicate_faces")
+        call("sgr_mesh_clean_duplicate_faces", dev, int(f.shape[0]), ptr(f), ptr(perm), ptr(keep))
         f = f[keep.bool()].contiguous()
     if duplicated_vertices and V:
         perm = _lexsort_rows(v.view(torch.int32))
         start = torch.empty(V, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.sgr_mesh_clean_duplicate_verts(V, _vp(v), _vp(perm), _vp(start), st()), "sgr_mesh_clean_duplicate_verts")
+        call("sgr_mesh_clean_duplicate_verts", dev, V, ptr(v), ptr(perm), ptr(start))
         pos = torch.arange(V, device=dev)
         leader = torch.cummax(torch.where(start == 1, pos, torch.zeros_like(pos)), 0).values
         vmap = torch.empty(V, dtype=torch.int64, device=dev)
@@ -250,9 +203,7 @@ def clean(verts: torch.Tensor, faces: torch.Tensor, degenerate: bool = True, dup
     while non_manifold_edges and f.shape[0] and V:
         skey, order = _sorted_incidences(f, V)
         remove = torch.zeros(f.shape[0], dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.sgr_mesh_clean_nonmanifold(V, int(f.shape[0]), _vp(skey), _vp(order), _vp(v), _vp(f), _vp(remove), st()),
-                   "sgr_mesh_clean_nonmanifold")
+        call("sgr_mesh_clean_nonmanifold", dev, V, int(f.shape[0]), ptr(skey), ptr(order), ptr(v), ptr(f), ptr(remove))
         if int(remove.sum()) == 0:
             break
         f = f[remove == 0].contiguous()
@@ -260,16 +211,13 @@ def clean(verts: torch.Tensor, faces: torch.Tensor, degenerate: bool = True, dup
     if V == 0 or F_ == 0:
         return v[:0], torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.full((V,), -1, dtype=torch.int64, device=dev)
     ref = torch.zeros(V, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.sgr_mesh_clean_referenced(V, F_, _vp(f), _vp(ref), st()), "sgr_mesh_clean_referenced")
+    call("sgr_mesh_clean_referenced", dev, V, F_, ptr(f), ptr(ref))
     vpos = torch.cumsum(ref, 0, dtype=torch.int64)
     fkeep = ones(F_)
     fpos = torch.cumsum(fkeep, 0, dtype=torch.int64)
     v2, f2 = torch.empty_like(v), torch.empty_like(f)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_decimate_compact(V, F_, _vp(ref), _vp(vpos), _vp(fkeep), _vp(fpos), None, None, _vp(v), _vp(f), None, None, _vp(v2),
-                                           _vp(f2), st())
-    _check(rc, "sgr_mesh_decimate_compact")
+    call("sgr_mesh_decimate_compact", dev, V, F_, ptr(ref), ptr(vpos), ptr(fkeep), ptr(fpos), None, None, ptr(v), ptr(f), None, None,
+         ptr(v2), ptr(f2))
     n_verts = int(vpos[-1])
     new_id = torch.where(ref > 0, vpos - 1, torch.full_like(vpos, -1))
     return v2[:n_verts], f2.to(torch.int64), new_id[vmap]

@@ -25,11 +25,11 @@ There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 
 import torch
 
 from . import _lib
+from ._call import call, ptr as p
 from . import decimate as _decimate
 from . import field as _field
 from . import marching_cubes as _mc
@@ -74,21 +74,13 @@ def density_grid(X, Y, Z, centers, inv_scaled_rot, strengths, K: int = 16, point
     n_max = min(points_per_pass, N)
     pts_buf = torch.empty(n_max, 3, dtype=torch.float32, device=dev)
     opac = torch.empty(n_max, int(K), dtype=torch.float32, device=dev)
-    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    p = _field._p
     for start in range(0, N, points_per_pass):
         n = min(points_per_pass, N - start)
         pts = pts_buf[:n]
-        with torch.cuda.device(dev):
-            rc = lib.sgr_grid_points(nx, ny, nz, p(X), p(Y), p(Z), start, n, p(pts), stream())
-        if rc < 0:
-            raise RuntimeError(f"sgr_grid_points failed ({rc}): {_lib.last_error()}")
+        call("sgr_grid_points", dev, nx, ny, nz, p(X), p(Y), p(Z), start, n, p(pts))
         idx = knn_points(pts[None], ce[None], K=int(K)).idx[0]
         dens = flat[start:start + n]
-        with torch.cuda.device(dev):
-            rc = lib.sgr_density_field_forward(n, int(K), p(pts), p(idx), p(ce), p(Bm), p(st), 1.0, p(opac), p(dens), p(packed), stream())
-        if rc < 0:
-            raise RuntimeError(f"sgr_density_field_forward failed ({rc}): {_lib.last_error()}")
+        call("sgr_density_field_forward", dev, n, int(K), p(pts), p(idx), p(ce), p(Bm), p(st), 1.0, p(opac), p(dens), p(packed))
     if zero_inside is not None:
         lo, hi = float(zero_inside[0]), float(zero_inside[1])
         mx, my, mz = ((a > lo) & (a < hi) for a in (X, Y, Z))

@@ -13,24 +13,17 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._call import call, ptr, stream
 
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+_p, _stream = ptr, stream    # the names tests/test_gpu_field.py drives the C ABI through
 
 
 def _pack(lib, ce, Bm, st):
-    """one 64-byte record per Gaussian for the kernels' neighbour gathers (sgr_pack_gaussians)"""
+    """one 64-byte record per Gaussian for the kernels' neighbour gathers (sgr_pack_gaussians).  `lib` is no longer read (`call` loads
+    the library itself); it stays in the signature because tests/test_gpu_field.py and scripts/marching_cubes_bench.py pass it."""
     P, dev = ce.shape[0], ce.device
     packed = torch.empty(P, 16, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_pack_gaussians(P, _p(ce), _p(Bm), _p(st), _p(packed), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_pack_gaussians failed ({rc})")
+    call("sgr_pack_gaussians", dev, P, ptr(ce), ptr(Bm), ptr(st), ptr(packed))
     return packed
 
 
@@ -54,11 +47,8 @@ class _DensityField(torch.autograd.Function):
         opac = torch.empty(N, K, device=dev)
         dens = torch.empty(N, device=dev)
         packed = _pack(lib, ce, Bm, st)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_density_field_forward(N, K, _p(xs), _p(nb), _p(ce), _p(Bm), _p(st), float(density_factor), _p(opac),
-                                               _p(dens), _p(packed), _stream(dev))
-        if rc < 0:
-            raise RuntimeError(f"sgr_density_field_forward failed ({rc})")
+        call("sgr_density_field_forward", dev, N, K, ptr(xs), ptr(nb), ptr(ce), ptr(Bm), ptr(st), float(density_factor), ptr(opac),
+             ptr(dens), ptr(packed))
         ctx.save_for_backward(xs, nb, ce, Bm, st, packed)
         ctx.factor = float(density_factor)
         ctx.shapes = (inv_scaled_rot.shape, strengths.shape)
@@ -78,16 +68,12 @@ class _DensityField(torch.autograd.Function):
             # one integer atomic per pair + a per-Gaussian gather (every output row is written)
             dce = torch.empty(P, 3, device=dev); dB = torch.empty(P, 9, device=dev); dst = torch.empty(P, device=dev)
             scratch = torch.empty(lib.sgr_density_field_backward_scratch_bytes(N, K, P), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.sgr_density_field_backward_gather(N, K, P, _p(xs), _p(nb), _p(ce), _p(Bm), _p(st), ctx.factor, _p(go), _p(gd),
-                                                           _p(dx), _p(dce), _p(dB), _p(dst), _p(scratch), _p(packed), _stream(dev))
+            call("sgr_density_field_backward_gather", dev, N, K, P, ptr(xs), ptr(nb), ptr(ce), ptr(Bm), ptr(st), ctx.factor, ptr(go), ptr(gd),
+                 ptr(dx), ptr(dce), ptr(dB), ptr(dst), ptr(scratch), ptr(packed))
         else:
             dce = torch.zeros(P, 3, device=dev); dB = torch.zeros(P, 9, device=dev); dst = torch.zeros(P, device=dev)
-            with torch.cuda.device(dev):
-                rc = lib.sgr_density_field_backward(N, K, _p(xs), _p(nb), _p(ce), _p(Bm), _p(st), ctx.factor, _p(go), _p(gd), _p(dx),
-                                                    _p(dce), _p(dB), _p(dst), _p(packed), _stream(dev))
-        if rc < 0:
-            raise RuntimeError(f"sgr_density_field_backward failed ({rc})")
+            call("sgr_density_field_backward", dev, N, K, ptr(xs), ptr(nb), ptr(ce), ptr(Bm), ptr(st), ctx.factor, ptr(go), ptr(gd), ptr(dx),
+                 ptr(dce), ptr(dB), ptr(dst), ptr(packed))
         Bshape, sshape = ctx.shapes
         return dx, None, dce, dB.reshape(Bshape), dst.reshape(sshape), None
 
@@ -95,31 +81,23 @@ class _DensityField(torch.autograd.Function):
 class _ScaledRotation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, quaternions, scaling, inverse_scales):
-        lib = _lib.load()
         if not quaternions.is_cuda:
             raise RuntimeError("the HIP scaled-rotation op needs tensors on a ROCm device; there is no CPU fallback")
         q, s = quaternions.contiguous().float(), scaling.contiguous().float()
         P, dev = q.shape[0], q.device
         out = torch.empty(P, 3, 3, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_scaled_rotation_forward(P, _p(q), _p(s), int(bool(inverse_scales)), _p(out), _stream(dev))
-        if rc < 0:
-            raise RuntimeError(f"sgr_scaled_rotation_forward failed ({rc})")
+        call("sgr_scaled_rotation_forward", dev, P, ptr(q), ptr(s), int(bool(inverse_scales)), ptr(out))
         ctx.save_for_backward(q, s)
         ctx.inverse = int(bool(inverse_scales))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         q, s = ctx.saved_tensors
         P, dev = q.shape[0], q.device
         dq, ds = torch.empty_like(q), torch.empty_like(s)
         g = g.contiguous().float()  # (kept referenced until the call is enqueued: a temporary's block goes back to the allocator at once)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_scaled_rotation_backward(P, _p(q), _p(s), ctx.inverse, _p(g), _p(dq), _p(ds), _stream(dev))
-        if rc < 0:
-            raise RuntimeError(f"sgr_scaled_rotation_backward failed ({rc})")
+        call("sgr_scaled_rotation_backward", dev, P, ptr(q), ptr(s), ctx.inverse, ptr(g), ptr(dq), ptr(ds))
         return dq, ds, None
 
 
@@ -154,12 +132,8 @@ def level_set_points(world_points, nbr_idx, cam_center, centers, inv_scaled_rot,
     nrm = torch.empty(L, N, 3, device=dev) if return_normals else None
     lv = (C.c_float * L)(*[float(v) for v in surface_levels])
     packed = _pack(lib, ce, Bm, st)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_level_set_points(N, K, _p(wp), _p(nb), _p(cam), _p(ce), _p(Bm), _p(st), _p(gstd), L, lv,
-                                      int(n_points_in_range), float(range_size), float(density_factor), _p(valid), _p(pts),
-                                      _p(nrm), _p(packed), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_level_set_points failed ({rc})")
+    call("sgr_level_set_points", dev, N, K, ptr(wp), ptr(nb), ptr(cam), ptr(ce), ptr(Bm), ptr(st), ptr(gstd), L, lv, int(n_points_in_range),
+         float(range_size), float(density_factor), ptr(valid), ptr(pts), ptr(nrm), ptr(packed))
     if raw:
         return valid, pts, nrm
     out = {}

@@ -17,6 +17,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._call import call
 
 
 STATS = {"fused_steps": 0, "fallback_steps": 0, "last_fallback_reason": None}   # (diagnostics: which path the steps took)
@@ -63,7 +64,7 @@ class FusedAdam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
+        _lib.load()  # (a missing library fails here, before any state changes)
         # Everything a launch can reject is prepared BEFORE any state changes (a step that failed half way would leave some
         # parameters updated and some step counters advanced): dense, 16-byte aligned storage for parameter, gradient and moments.
         # `.contiguous()` returns the SAME storage for a contiguous tensor at an odd offset (a `[1:]` slice): those get a real copy.
@@ -99,15 +100,11 @@ class FusedAdam(torch.optim.Adam):
                 chunk = items[k0:k0 + 8]
                 T = len(chunk)
                 ptrs = lambda sel: (C.c_void_p * T)(*[sel(it).data_ptr() for it in chunk])
-                with torch.cuda.device(dev):
-                    rc = lib.sgr_adam_step_multi(
-                        T, (C.c_longlong * T)(*[it[1].numel() for it in chunk]), ptrs(lambda it: it[3]), ptrs(lambda it: it[4]),
-                        ptrs(lambda it: it[5]), ptrs(lambda it: it[6]), (C.c_float * T)(*[float(it[0]["lr"]) for it in chunk]),
-                        (C.c_float * T)(*[float(it[0]["betas"][0]) for it in chunk]), (C.c_float * T)(*[float(it[0]["betas"][1]) for it in chunk]),
-                        (C.c_float * T)(*[float(it[0]["eps"]) for it in chunk]), (C.c_int * T)(*[int(it[2]["step"]) for it in chunk]),
-                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-                if rc < 0:
-                    raise RuntimeError(f"sgr_adam_step_multi failed ({rc})")
+                call("sgr_adam_step_multi", dev,
+                     T, (C.c_longlong * T)(*[it[1].numel() for it in chunk]), ptrs(lambda it: it[3]), ptrs(lambda it: it[4]),
+                     ptrs(lambda it: it[5]), ptrs(lambda it: it[6]), (C.c_float * T)(*[float(it[0]["lr"]) for it in chunk]),
+                     (C.c_float * T)(*[float(it[0]["betas"][0]) for it in chunk]), (C.c_float * T)(*[float(it[0]["betas"][1]) for it in chunk]),
+                     (C.c_float * T)(*[float(it[0]["eps"]) for it in chunk]), (C.c_int * T)(*[int(it[2]["step"]) for it in chunk]))
         for group, p, state, dense, grad, m, v in plan:
             if dense is not p:
                 p.copy_(dense)

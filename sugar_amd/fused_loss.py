@@ -7,11 +7,10 @@ stock-PyTorch restatement for CPU use and as the parity reference).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._call import call, ptr
 
 
 class _L1SSIM(torch.autograd.Function):
@@ -26,12 +25,7 @@ class _L1SSIM(torch.autograd.Function):
         dev = image.device
         scratch = torch.empty(lib.sgr_l1_ssim_scratch_bytes(Cn, W, H), dtype=torch.uint8, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_l1_ssim_forward(Cn, W, H, C.c_void_p(image.data_ptr()), C.c_void_p(gt.data_ptr()), float(lambda_dssim),
-                                         C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_l1_ssim_forward failed ({rc})")
+        call("sgr_l1_ssim_forward", dev, Cn, W, H, ptr(image), ptr(gt), float(lambda_dssim), ptr(scratch), ptr(out))
         ctx.save_for_backward(image, gt, scratch)
         ctx.lambda_dssim = float(lambda_dssim)
         return out[0]
@@ -39,18 +33,11 @@ class _L1SSIM(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss):
         image, gt, scratch = ctx.saved_tensors
-        lib = _lib.load()
         Cn, H, W = image.shape
         dev = image.device
         g = grad_loss.to(dtype=torch.float32, device=dev).reshape(1).contiguous()
         grad_img = torch.empty_like(image)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_l1_ssim_backward(Cn, W, H, C.c_void_p(image.data_ptr()), C.c_void_p(gt.data_ptr()), ctx.lambda_dssim,
-                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(g.data_ptr()),
-                                          C.c_void_p(grad_img.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_l1_ssim_backward failed ({rc})")
+        call("sgr_l1_ssim_backward", dev, Cn, W, H, ptr(image), ptr(gt), ctx.lambda_dssim, ptr(scratch), ptr(g), ptr(grad_img))
         return grad_img, None, None
 
 
@@ -72,30 +59,18 @@ class _SSIM(torch.autograd.Function):
         dev = image.device
         scratch = torch.empty(lib.sgr_l1_ssim_scratch_bytes(Cn, W, H), dtype=torch.uint8, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_l1_ssim_forward(Cn, W, H, C.c_void_p(image.data_ptr()), C.c_void_p(gt.data_ptr()), 1.0,
-                                         C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_l1_ssim_forward failed ({rc})")
+        call("sgr_l1_ssim_forward", dev, Cn, W, H, ptr(image), ptr(gt), 1.0, ptr(scratch), ptr(out))
         ctx.save_for_backward(image, gt, scratch)
         return out[2]
 
     @staticmethod
     def backward(ctx, grad_ssim):
         image, gt, scratch = ctx.saved_tensors
-        lib = _lib.load()
         Cn, H, W = image.shape
         dev = image.device
         g = (-grad_ssim).to(dtype=torch.float32, device=dev).reshape(1).contiguous()   # loss(lambda = 1) = 1 - ssim
         grad_img = torch.empty_like(image)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_l1_ssim_backward(Cn, W, H, C.c_void_p(image.data_ptr()), C.c_void_p(gt.data_ptr()), 1.0,
-                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(g.data_ptr()),
-                                          C.c_void_p(grad_img.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_l1_ssim_backward failed ({rc})")
+        call("sgr_l1_ssim_backward", dev, Cn, W, H, ptr(image), ptr(gt), 1.0, ptr(scratch), ptr(g), ptr(grad_img))
         return grad_img, None
 
 

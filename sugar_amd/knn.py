@@ -7,12 +7,12 @@
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
+from ._call import call, ptr
 
 
 class _KNN(NamedTuple):
@@ -39,16 +39,11 @@ def distCUDA2(points: torch.Tensor, method: str = "auto") -> torch.Tensor:
     P = points.shape[0]
     out = torch.zeros(P, dtype=torch.float32, device=points.device)  # spatial.cu:19 (full 0.0)
     if P:
-        with torch.cuda.device(points.device):
-            stream = C.c_void_p(torch.cuda.current_stream(points.device).cuda_stream)
-            if method == "grid" or (method == "auto" and P >= GRID_THRESHOLD):
-                scratch = torch.empty(lib.sgr_knn_grid_scratch_bytes(P), dtype=torch.uint8, device=points.device)
-                rc = lib.sgr_dist2_grid(P, C.c_void_p(points.data_ptr()), C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(scratch.data_ptr()), stream)
-            else:
-                rc = lib.sgr_dist2(P, C.c_void_p(points.data_ptr()), C.c_void_p(out.data_ptr()), stream)
-        if rc < 0:
-            raise RuntimeError(f"sgr_dist2 failed ({rc})")
+        if method == "grid" or (method == "auto" and P >= GRID_THRESHOLD):
+            scratch = torch.empty(lib.sgr_knn_grid_scratch_bytes(P), dtype=torch.uint8, device=points.device)
+            call("sgr_dist2_grid", points.device, P, ptr(points), ptr(out), ptr(scratch))
+        else:
+            call("sgr_dist2", points.device, P, ptr(points), ptr(out))
     return out
 
 
@@ -69,17 +64,11 @@ def knn_points(p1: torch.Tensor, p2: torch.Tensor, lengths1=None, lengths2=None,
     K = next(k for k in SUPPORTED_K if k >= K_req)  # the kernels are instantiated for these; a prefix of a longer list is exact
     d = torch.empty(N, K, dtype=torch.float32, device=q.device)
     i = torch.empty(N, K, dtype=torch.int64, device=q.device)
-    with torch.cuda.device(q.device):
-        stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        if method == "grid" or (method == "auto" and M >= GRID_THRESHOLD):
-            scratch = torch.empty(lib.sgr_knn_grid_scratch_bytes(M), dtype=torch.uint8, device=q.device)
-            rc = lib.sgr_knn_grid(N, C.c_void_p(q.data_ptr()), M, C.c_void_p(r.data_ptr()), int(K), C.c_void_p(d.data_ptr()),
-                                  C.c_void_p(i.data_ptr()), C.c_void_p(scratch.data_ptr()), stream)
-        else:
-            rc = lib.sgr_knn(N, C.c_void_p(q.data_ptr()), M, C.c_void_p(r.data_ptr()), int(K), C.c_void_p(d.data_ptr()),
-                             C.c_void_p(i.data_ptr()), stream)
-    if rc < 0:
-        raise RuntimeError(f"sgr_knn failed ({rc})")
+    if method == "grid" or (method == "auto" and M >= GRID_THRESHOLD):
+        scratch = torch.empty(lib.sgr_knn_grid_scratch_bytes(M), dtype=torch.uint8, device=q.device)
+        call("sgr_knn_grid", q.device, N, ptr(q), M, ptr(r), int(K), ptr(d), ptr(i), ptr(scratch))
+    else:
+        call("sgr_knn", q.device, N, ptr(q), M, ptr(r), int(K), ptr(d), ptr(i))
     if K != K_req:
         d, i = d[:, :K_req].contiguous(), i[:, :K_req].contiguous()
     return _KNN(d[None], i[None], r[i][None] if return_nn else None)

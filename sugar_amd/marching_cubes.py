@@ -14,31 +14,16 @@ numbered by a scan in grid order: the result is bit-identical between runs.
 device; `mc_emit` takes the two integers).  Nothing else in this module waits on the device.  There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._call import call, csr, need_gpu, ptr
 
 MAX_POINTS = 2 ** 31  # nx * ny * nz must stay below this
 
 
-def _vp(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _check(rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name} failed ({rc}): {_lib.last_error()}")
-
-
 def _volume(volume, level):
-    if not torch.is_tensor(volume) or not volume.is_cuda:
-        raise RuntimeError("marching_cubes: volume must be a tensor on a ROCm device; there is no CPU fallback")
+    need_gpu("marching_cubes", volume=volume)
     if volume.dim() != 3 or volume.dtype != torch.float32:
         raise ValueError("marching_cubes: volume must be a float32 tensor of shape [nx, ny, nz]")
     nx, ny, nz = (int(s) for s in volume.shape)
@@ -57,15 +42,12 @@ def mc_count(volume: torch.Tensor, level: float):
     dev = vol.device
     scratch = torch.empty(lib.sgr_marching_cubes_scratch_bytes(nx, ny, nz), dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_marching_cubes_count(nx, ny, nz, _vp(vol), level, _vp(scratch), _vp(counts), _stream(dev))
-    _check(rc, "sgr_marching_cubes_count")
+    call("sgr_marching_cubes_count", dev, nx, ny, nz, ptr(vol), level, ptr(scratch), ptr(counts))
     return (vol, level, scratch), counts
 
 
 def mc_emit(state, n_verts: int, n_faces: int):
     """the emit passes for the (V, F) read from `mc_count`'s counts: (verts[V,3] float32, faces[F,3] int64); no host synchronisation"""
-    lib = _lib.load()
     vol, level, scratch = state
     nx, ny, nz = (int(s) for s in vol.shape)
     n_verts, n_faces = int(n_verts), int(n_faces)
@@ -75,10 +57,7 @@ def mc_emit(state, n_verts: int, n_faces: int):
     verts = torch.empty(n_verts, 3, dtype=torch.float32, device=dev)
     faces = torch.empty(n_faces, 3, dtype=torch.int64, device=dev)
     if n_verts or n_faces:
-        with torch.cuda.device(dev):
-            rc = lib.sgr_marching_cubes_emit(nx, ny, nz, _vp(vol), level, _vp(scratch), n_verts, n_faces, _vp(verts), _vp(faces),
-                                             _stream(dev))
-        _check(rc, "sgr_marching_cubes_emit")
+        call("sgr_marching_cubes_emit", dev, nx, ny, nz, ptr(vol), level, ptr(scratch), n_verts, n_faces, ptr(verts), ptr(faces))
     return verts, faces
 
 
@@ -93,12 +72,9 @@ def marching_cubes(volume: torch.Tensor, level: float):
 def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """normals[V,3]: per vertex the sum of the area-weighted normals (b - a) x (c - a) of its faces, added in ascending (face, corner)
     order, normalised; zero where a vertex has no face or no area around it.  No host synchronisation."""
-    for name, t in (("verts", verts), ("faces", faces)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"vertex_normals: {name} must be a tensor on a ROCm device; there is no CPU fallback")
+    need_gpu("vertex_normals", verts=verts, faces=faces)
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError("vertex_normals: verts must be [V,3] and faces [F,3]")
-    lib = _lib.load()
     v = verts.detach().to(torch.float32).contiguous()
     f = faces.detach().to(torch.int64).contiguous()
     V, F_ = int(v.shape[0]), int(f.shape[0])
@@ -107,13 +83,7 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         return normals
     if 3 * F_ >= MAX_POINTS:
         raise ValueError("vertex_normals: 3 F must stay below 2^31")
-    # the vertex -> (face, corner) list, as sugar_amd.mesh_bind builds it (a face naming a vertex outside [0, V) is skipped by the kernel)
-    flat = f.reshape(-1).clamp(0, V - 1)
-    sorted_flat, items = torch.sort(flat, stable=True)
-    items = items.to(torch.int32)
-    # (searchsorted, not bincount: bincount reads its input's maximum on the host)
-    offsets = torch.searchsorted(sorted_flat, torch.arange(V + 1, device=v.device)).to(torch.int32)
-    with torch.cuda.device(v.device):
-        rc = lib.sgr_mesh_vertex_normals(V, F_, _vp(v), _vp(f), _vp(offsets), _vp(items), _vp(normals), _stream(v.device))
-    _check(rc, "sgr_mesh_vertex_normals")
+    # the vertex -> (face, corner) list (a face naming a vertex outside [0, V) is skipped by the kernel)
+    offsets, items = csr(f.clamp(0, V - 1), V)
+    call("sgr_mesh_vertex_normals", v.device, V, F_, ptr(v), ptr(f), ptr(offsets), ptr(items), ptr(normals))
     return normals

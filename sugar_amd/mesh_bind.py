@@ -18,33 +18,14 @@ Vertex gradients are deterministic: per-(face, corner) and per-(pair, slot) cont
 the order of its list; there are no float atomics.  There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
+from ._call import call, csr, need_gpu as _need_gpu, ptr
 
 CACHE_ENTRIES = 4
-
-
-def _vp(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _csr(flat: torch.Tensor, n_rows: int):
-    """(offsets[n_rows+1] int32, items[len(flat)] int32): row r owns items[offsets[r]:offsets[r+1]] = the positions i with
-    flat[i] == r, ascending"""
-    flat = flat.reshape(-1).to(torch.int64)
-    items = torch.argsort(flat, stable=True)
-    counts = torch.bincount(flat, minlength=n_rows)[:n_rows]
-    offsets = torch.zeros(n_rows + 1, dtype=torch.int64, device=flat.device)
-    offsets[1:] = torch.cumsum(counts, 0)
-    return offsets.to(torch.int32).contiguous(), items.to(torch.int32).contiguous()
 
 
 def edge_pairs(faces: torch.Tensor, n_verts: int):
@@ -98,11 +79,11 @@ class MeshTopology:
         if bool(((f < 0) | (f >= self.n_verts)).any()):
             raise ValueError(f"MeshTopology: a face names a vertex outside [0, {self.n_verts})")
         self.faces = f.to(torch.int32).contiguous()
-        self.vert_offsets, self.vert_items = _csr(f, self.n_verts)
+        self.vert_offsets, self.vert_items = csr(f, self.n_verts)
         pairs, self.pair_faces = edge_pairs(f, self.n_verts)
         self.n_pairs = int(pairs.shape[0])
         self.pairs = pairs.to(torch.int32).contiguous()
-        self.pair_offsets, self.pair_items = _csr(pairs, self.n_verts)
+        self.pair_offsets, self.pair_items = csr(pairs, self.n_verts)
         self.device = f.device
         self._keepalive = faces        # the cache key holds its data_ptr: keep the storage from being reused
 
@@ -126,20 +107,9 @@ class MeshTopology:
         cls._cache.clear()
 
 
-def _need_gpu(what, **tensors):
-    for name, t in tensors.items():
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a tensor on a ROCm device; there is no CPU fallback")
-
-
 def _f32c(t):
     t = t.detach()
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
-
-
-def _check(rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name} failed ({rc}): {_lib.last_error()}")
 
 
 def _bary(bary, device):
@@ -153,7 +123,6 @@ def _bary(bary, device):
 
 def _backward(topo, n, verts, bary, scales, cplx, g_points, g_scaling, g_quats):
     """one sgr_mesh_bind_backward call; returns (d_verts, d_scales, d_cplx), None where not requested"""
-    lib = _lib.load()
     mesh = g_points is not None or g_quats is not None
     dev = (g_points if g_points is not None else g_quats if g_quats is not None else g_scaling).device
     F_, V = topo.n_faces, topo.n_verts
@@ -161,11 +130,8 @@ def _backward(topo, n, verts, bary, scales, cplx, g_points, g_scaling, g_quats):
     contrib = torch.empty(3 * F_, 3, dtype=torch.float32, device=dev) if mesh else None
     d_scales = torch.empty(F_ * n, 2, dtype=torch.float32, device=dev) if g_scaling is not None else None
     d_cplx = torch.empty(F_ * n, 2, dtype=torch.float32, device=dev) if g_quats is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.sgr_mesh_bind_backward(F_, n, V, _vp(verts), _vp(topo.faces), _vp(bary), _vp(scales), _vp(cplx), _vp(g_points),
-                                        _vp(g_scaling), _vp(g_quats), _vp(topo.vert_offsets), _vp(topo.vert_items), _vp(contrib),
-                                        _vp(d_verts), _vp(d_scales), _vp(d_cplx), _stream(dev))
-    _check(rc, "sgr_mesh_bind_backward")
+    call("sgr_mesh_bind_backward", dev, F_, n, V, ptr(verts), ptr(topo.faces), ptr(bary), ptr(scales), ptr(cplx), ptr(g_points),
+         ptr(g_scaling), ptr(g_quats), ptr(topo.vert_offsets), ptr(topo.vert_items), ptr(contrib), ptr(d_verts), ptr(d_scales), ptr(d_cplx))
     return d_verts, d_scales, d_cplx
 
 
@@ -175,10 +141,8 @@ class _BoundPoints(torch.autograd.Function):
         v = _f32c(verts)
         n = int(bary.shape[0])
         out = torch.empty(topo.n_faces * n, 3, dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            rc = _lib.load().sgr_mesh_bind_forward(topo.n_faces, n, topo.n_verts, _vp(v), _vp(topo.faces), _vp(bary), None, None, None,
-                                                   _vp(out), None, None, _stream(v.device))
-        _check(rc, "sgr_mesh_bind_forward")
+        call("sgr_mesh_bind_forward", v.device, topo.n_faces, n, topo.n_verts, ptr(v), ptr(topo.faces), ptr(bary), None, None, None,
+             ptr(out), None, None)
         ctx.topo, ctx.bary, ctx.n = topo, bary, n
         return out
 
@@ -194,24 +158,18 @@ class _BoundScaling(torch.autograd.Function):
         s = _f32c(scales)
         P = int(s.shape[0])
         out = torch.empty(P, 3, dtype=torch.float32, device=s.device)
-        with torch.cuda.device(s.device):
-            rc = _lib.load().sgr_mesh_bind_forward(P, 1, 0, None, None, None, _vp(s), None, _vp(thickness), None, _vp(out), None,
-                                                   _stream(s.device))
-        _check(rc, "sgr_mesh_bind_forward")
+        call("sgr_mesh_bind_forward", s.device, P, 1, 0, None, None, None, ptr(s), None, ptr(thickness), None, ptr(out), None)
         ctx.save_for_backward(s)
         return out
 
     @staticmethod
     def backward(ctx, grad):
         (s,) = ctx.saved_tensors
-        lib = _lib.load()
         g = _f32c(grad)
         P = int(s.shape[0])
         d_scales = torch.empty(P, 2, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            rc = lib.sgr_mesh_bind_backward(P, 1, 0, None, None, None, _vp(s), None, None, _vp(g), None, None, None, None, None,
-                                            _vp(d_scales), None, _stream(g.device))
-        _check(rc, "sgr_mesh_bind_backward")
+        call("sgr_mesh_bind_backward", g.device, P, 1, 0, None, None, None, ptr(s), None, None, ptr(g), None, None, None, None, None,
+             ptr(d_scales), None)
         return d_scales, None
 
 
@@ -220,10 +178,8 @@ class _BoundQuaternions(torch.autograd.Function):
     def forward(ctx, verts, cplx, topo, n):
         v, z = _f32c(verts), _f32c(cplx)
         out = torch.empty(topo.n_faces * n, 4, dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            rc = _lib.load().sgr_mesh_bind_forward(topo.n_faces, n, topo.n_verts, _vp(v), _vp(topo.faces), None, None, _vp(z), None,
-                                                   None, None, _vp(out), _stream(v.device))
-        _check(rc, "sgr_mesh_bind_forward")
+        call("sgr_mesh_bind_forward", v.device, topo.n_faces, n, topo.n_verts, ptr(v), ptr(topo.faces), None, None, ptr(z), None, None,
+             None, ptr(out))
         ctx.save_for_backward(v, z)
         ctx.topo, ctx.n = topo, n
         return out
@@ -280,10 +236,7 @@ class _NormalConsistency(torch.autograd.Function):
         v = _f32c(verts)
         loss = torch.empty(1, dtype=torch.float32, device=v.device)
         scratch = torch.empty(lib.sgr_normal_consistency_scratch_bytes() // 8, dtype=torch.float64, device=v.device)
-        with torch.cuda.device(v.device):
-            rc = lib.sgr_normal_consistency_forward(topo.n_pairs, topo.n_verts, _vp(v), _vp(topo.pairs), _vp(scratch), _vp(loss),
-                                                    _stream(v.device))
-        _check(rc, "sgr_normal_consistency_forward")
+        call("sgr_normal_consistency_forward", v.device, topo.n_pairs, topo.n_verts, ptr(v), ptr(topo.pairs), ptr(scratch), ptr(loss))
         ctx.save_for_backward(v)
         ctx.topo = topo
         return loss.reshape(())
@@ -295,11 +248,8 @@ class _NormalConsistency(torch.autograd.Function):
         g = _f32c(grad).reshape(1)
         d_verts = torch.empty(topo.n_verts, 3, dtype=torch.float32, device=v.device)
         contrib = torch.empty(4 * topo.n_pairs, 3, dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            rc = _lib.load().sgr_normal_consistency_backward(topo.n_pairs, topo.n_verts, _vp(v), _vp(topo.pairs), _vp(g),
-                                                             _vp(topo.pair_offsets), _vp(topo.pair_items), _vp(contrib), _vp(d_verts),
-                                                             _stream(v.device))
-        _check(rc, "sgr_normal_consistency_backward")
+        call("sgr_normal_consistency_backward", v.device, topo.n_pairs, topo.n_verts, ptr(v), ptr(topo.pairs), ptr(g),
+             ptr(topo.pair_offsets), ptr(topo.pair_items), ptr(contrib), ptr(d_verts))
         return d_verts, None
 
 

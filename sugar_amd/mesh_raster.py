@@ -11,11 +11,10 @@ host logic of the shim and to write fixtures with the reference's own sampler); 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._call import call, ptr
 
 MAX_FACES_PER_PIXEL = 16
 _backend = None  # tests only: callable(face_verts[F,3,3] cpu tensor, image_size, K, perspective_correct, cull_backfaces) -> 4 tensors [H,W,K(,3)]
@@ -67,20 +66,15 @@ def rasterize_face_verts(face_verts: torch.Tensor, mesh_to_face_first_idx, num_f
         return t.data_ptr()
 
     cb = _lib.ALLOC_FN(alloc)
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for n in range(N):
-            F = count[n]
-            nbytes = lib.sgr_rasterize_meshes_scratch_bytes(F, W, H)
-            scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-            keep.append(scratch)
-            sub = fv[first[n]:first[n] + F]
-            rc = lib.sgr_rasterize_meshes(vp(sub) if F else None, F, first[n], W, H, float(blur_radius), K, int(bool(perspective_correct)),
-                                          0, int(bool(cull_backfaces)), vp(scratch), scratch.numel(), cb, None, vp(p2f[n]), vp(zbuf[n]),
-                                          None if bary is None else vp(bary[n]), None if dists is None else vp(dists[n]), stream)
-            if rc < 0:
-                raise RuntimeError(f"sgr_rasterize_meshes failed ({rc}): {_lib.last_error()}")
+    for n in range(N):
+        F = count[n]
+        nbytes = lib.sgr_rasterize_meshes_scratch_bytes(F, W, H)
+        scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+        keep.append(scratch)
+        sub = fv[first[n]:first[n] + F]
+        call("sgr_rasterize_meshes", dev, ptr(sub) if F else None, F, first[n], W, H, float(blur_radius), K, int(bool(perspective_correct)),
+             0, int(bool(cull_backfaces)), ptr(scratch), scratch.numel(), cb, None, ptr(p2f[n]), ptr(zbuf[n]),
+             None if bary is None else ptr(bary[n]), None if dists is None else ptr(dists[n]))
     return p2f, zbuf, bary, dists
 
 
@@ -91,7 +85,6 @@ def splat_face_verts(points: torch.Tensor, scaling: torch.Tensor, quaternions: t
     world_to_view / projection: the camera's 4x4 matrices in pytorch3d's row-vector convention ([1,4,4] or [4,4])."""
     if not points.is_cuda:
         raise RuntimeError("splat_face_verts needs tensors on a ROCm device; there is no CPU fallback")
-    lib = _lib.load()
     dev = points.device
     f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
     pts, sc, q, prim = f32(points), f32(scaling), f32(quaternions), f32(primitive_verts)
@@ -100,11 +93,6 @@ def splat_face_verts(points: torch.Tensor, scaling: torch.Tensor, quaternions: t
     if sc.shape != (P, 3) or q.shape != (P, 4) or prim.shape != (4, 3) or V.numel() != 16 or Pm.numel() != 16:
         raise ValueError("splat_face_verts: expected points[P,3], scaling[P,3], quaternions[P,4], primitive_verts[4,3] and two 4x4 matrices")
     out = torch.empty(2 * P, 3, 3, dtype=torch.float32, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.sgr_splat_mesh_face_verts(P, vp(pts), vp(sc), vp(q), vp(prim), float(triangle_scale), vp(V), vp(Pm), vp(out),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"sgr_splat_mesh_face_verts failed ({rc}): {_lib.last_error()}")
+    call("sgr_splat_mesh_face_verts", dev, P, ptr(pts), ptr(sc), ptr(q), ptr(prim), float(triangle_scale), ptr(V), ptr(Pm), ptr(out))
     return out
 

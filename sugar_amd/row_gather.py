@@ -12,11 +12,10 @@ operation on it is the plain operation and returns plain tensors.  `sugar_amd.su
 properties `points`, `scaling`, `quaternions` and the method `get_normals` return their usual tensor viewed as this subclass."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._call import call, ptr
 
 MIN_ROWS = 32768   # below this the stock backward is as fast and its additions are ordered
 
@@ -47,11 +46,7 @@ class _RowGather(torch.autograd.Function):
         N = ix.numel()
         out = torch.empty(shape, dtype=torch.float32, device=dev)
         scratch = torch.empty(lib.sgr_scatter_add_rows_scratch_bytes(N, P), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_scatter_add_rows(N, C.c_void_p(ix.data_ptr()), C.c_void_p(g.data_ptr()), W, P, C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_scatter_add_rows failed ({rc})")
+        call("sgr_scatter_add_rows", dev, N, ptr(ix), ptr(g), W, P, ptr(out), ptr(scratch))
         return out, None
 
 

@@ -21,6 +21,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._call import call, ptr
 from .field import level_set_points, scaled_rotation
 from .knn import knn_points
 
@@ -37,24 +38,13 @@ def render_depth(means3D, scales, rotations, opacities, cam, bg_value: float = -
     ce = means3D.to(torch.float32).contiguous()
     vm = cam.viewmatrix.to(device=dev, dtype=torch.float32).contiguous()
     depth_rgb = torch.empty(ce.shape[0], 3, dtype=torch.float32, device=dev)   # (one launch: csrc/field.hip, k_view_depth_rgb)
-    with torch.cuda.device(dev):
-        rc = _lib.load().sgr_view_depth_rgb(int(ce.shape[0]), _p(ce), _p(vm), _p(depth_rgb), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_view_depth_rgb failed ({rc})")
+    call("sgr_view_depth_rgb", dev, int(ce.shape[0]), ptr(ce), ptr(vm), ptr(depth_rgb))
     st = GaussianRasterizationSettings(int(cam.image_height), int(cam.image_width), cam.tanfovx, cam.tanfovy,
                                        torch.full((3,), float(bg_value), device=dev), 1.0, cam.viewmatrix, cam.projmatrix, 0,
                                        cam.campos, False, False)
     img, _ = GaussianRasterizer(st)(means3D, torch.zeros_like(means3D), opacities, colors_precomp=depth_rgb, scales=scales,
                                     rotations=rotations)
     return img[0]
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def unproject_pixels(picked: torch.Tensor, depth_flat: torch.Tensor, cam) -> torch.Tensor:
@@ -68,11 +58,8 @@ def unproject_pixels(picked: torch.Tensor, depth_flat: torch.Tensor, cam) -> tor
     depth_flat = depth_flat.to(torch.float32).contiguous()
     vm = cam.viewmatrix.to(device=dev, dtype=torch.float32).contiguous()
     out = torch.empty(picked.shape[0], 3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().sgr_unproject_pixels(int(picked.shape[0]), _p(picked), _p(depth_flat), int(cam.image_width), int(cam.image_height),
-                                              float(cam.tanfovx), float(cam.tanfovy), _p(vm), _p(out), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_unproject_pixels failed ({rc})")
+    call("sgr_unproject_pixels", dev, int(picked.shape[0]), ptr(picked), ptr(depth_flat), int(cam.image_width), int(cam.image_height),
+         float(cam.tanfovx), float(cam.tanfovy), ptr(vm), ptr(out))
     return out
 
 
@@ -85,10 +72,7 @@ def view_std(means3D: torch.Tensor, rotations: torch.Tensor, scales: torch.Tenso
         q = q.clone()
     cc = campos.to(device=dev, dtype=torch.float32).reshape(3).contiguous()
     out = torch.empty(ce.shape[0], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().sgr_view_std(int(ce.shape[0]), _p(ce), _p(q), _p(sc), _p(cc), _p(out), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_view_std failed ({rc})")
+    call("sgr_view_std", dev, int(ce.shape[0]), ptr(ce), ptr(q), ptr(sc), ptr(cc), ptr(out))
     return out
 
 
@@ -154,11 +138,8 @@ def _sample_sync_free(means3D, scales, rotations, opacities, cam, depth_flat, n,
     picked = torch.empty(n, dtype=torch.int64, device=dev)
     words = torch.empty(2, dtype=torch.int32, device=dev)        # [count, n_valid]
     scratch = torch.empty(int(lib.sgr_pick_pixels_scratch_bytes(depth_flat.numel())), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_pick_pixels(int(depth_flat.numel()), _p(depth_flat), n, C.c_uint32(seed & 0xFFFFFFFF), _p(picked), _p(words),
-                                 C.c_void_p(words.data_ptr() + 4), _p(scratch), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_pick_pixels failed ({rc})")
+    call("sgr_pick_pixels", dev, int(depth_flat.numel()), ptr(depth_flat), n, C.c_uint32(seed & 0xFFFFFFFF), ptr(picked), ptr(words),
+         C.c_void_p(words.data_ptr() + 4), ptr(scratch))
     world = unproject_pixels(picked, depth_flat, cam)
     nbr = knn_points(world[None], means3D[None], K=K).idx[0]
     gaussian_idx = nbr[:, 0].contiguous()
@@ -175,12 +156,9 @@ def _sample_sync_free(means3D, scales, rotations, opacities, cam, depth_flat, n,
     gid_c = torch.empty(L, n, dtype=torch.int64, device=dev)
     counts = torch.empty(L, dtype=torch.int32, device=dev)
     scr2 = torch.empty(int(lib.sgr_compact_level_rows_scratch_bytes(n, L)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.sgr_compact_level_rows(n, L, _p(valid), _p(words), _p(pts), _p(nrm) if nrm is not None else None, _p(picked),
-                                        _p(gaussian_idx), _p(rows), _p(pts_c), _p(nrm_c) if nrm_c is not None else None, _p(pix_c),
-                                        _p(gid_c), _p(counts), _p(scr2), _stream(dev))
-    if rc < 0:
-        raise RuntimeError(f"sgr_compact_level_rows failed ({rc})")
+    call("sgr_compact_level_rows", dev, n, L, ptr(valid), ptr(words), ptr(pts), ptr(nrm), ptr(picked),
+         ptr(gaussian_idx), ptr(rows), ptr(pts_c), ptr(nrm_c), ptr(pix_c), ptr(gid_c), ptr(counts),
+         ptr(scr2))
     out = {}
     for i, lv in enumerate(surface_levels):
         out[lv] = dict(intersection_points=pts_c[i], pixel_idx=pix_c[i], gaussian_idx=gid_c[i], normals=nrm_c[i] if return_normals else None,

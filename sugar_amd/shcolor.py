@@ -8,15 +8,9 @@ reference:  `SuGaR.get_points_rgb = sugar_amd.shcolor.get_points_rgb`.  GPU tens
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._call import call, ptr
 
 
 def _rows(sh):
@@ -32,7 +26,6 @@ def _rows(sh):
 class _ShToRgb(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sh, positions, centers, directions, degree):
-        lib = _lib.load()
         if not sh.is_cuda:
             raise RuntimeError("the HIP SH->RGB op needs tensors on a ROCm device; there is no CPU fallback")
         sh_f = sh.float()
@@ -43,18 +36,14 @@ class _ShToRgb(torch.autograd.Function):
         cen = centers.reshape(-1, 3).contiguous().float() if centers is not None else None
         dirs = directions.contiguous().float() if directions is not None else None
         colors = torch.empty(P, 3, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_sh_to_rgb_forward(P, int(degree), M, _p(sh_rows), _p(pos), _p(cen), 0 if cen is None else cen.shape[0],
-                                           _p(dirs), _p(colors), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_sh_to_rgb_forward failed ({rc})")
+        call("sgr_sh_to_rgb_forward", dev, P, int(degree), M, ptr(sh_rows), ptr(pos), ptr(cen), 0 if cen is None else cen.shape[0],
+             ptr(dirs), ptr(colors))
         ctx.save_for_backward(sh_rows, pos, cen, dirs)
         ctx.meta = (int(degree), M, sh.shape)
         return colors
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         sh_rows, pos, cen, dirs = ctx.saved_tensors
         degree, M, shape = ctx.meta
         P, n = shape[0], shape[1]
@@ -64,12 +53,8 @@ class _ShToRgb(torch.autograd.Function):
         dpos = torch.empty(P, 3, device=dev) if (need_pos and pos is not None) else None
         ddir = torch.empty(P, 3, device=dev) if (need_dir and dirs is not None) else None
         g = g.contiguous().float()  # (kept referenced until the call is enqueued)
-        with torch.cuda.device(dev):
-            rc = lib.sgr_sh_to_rgb_backward(P, degree, M, _p(sh_rows), _p(pos), _p(cen), 0 if cen is None else cen.shape[0],
-                                            _p(dirs), _p(g), _p(dsh), _p(dpos), _p(ddir),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_sh_to_rgb_backward failed ({rc})")
+        call("sgr_sh_to_rgb_backward", dev, P, degree, M, ptr(sh_rows), ptr(pos), ptr(cen), 0 if cen is None else cen.shape[0], ptr(dirs),
+             ptr(g), ptr(dsh), ptr(dpos), ptr(ddir))
         if dsh is not None and M != n:
             dsh = dsh[:, :n]  # gradient of the slice that was passed in; autograd pads it back into the wide tensor
         return dsh, dpos, None, ddir, None

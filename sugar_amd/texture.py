@@ -16,12 +16,12 @@ and return value `(verts_uv, faces_uv, texture_img)`.  It needs none of pytorch3
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple
 
 import torch
 
 from . import _lib
+from ._call import call, ptr
 
 SH_C0 = 0.28209479177387814
 
@@ -62,10 +62,6 @@ def uv_layout(T: int, s: int, device):
 def _check(cond, msg):
     if not cond:
         raise ValueError(msg)
-
-
-def _vp(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class TextureBaker:
@@ -115,15 +111,9 @@ class TextureBaker:
     def reset(self) -> None:
         """(re)start baking: the atlas kernel writes the init image and clears the counters and the winner tags"""
         self.view = 0
-        with torch.cuda.device(self.device):
-            rc = _lib.load().sgr_texture_atlas(self.T, self.n, self.s, int(self._verts.shape[0]), _vp(self._verts), _vp(self._faces),
-                                               _vp(self._points), _vp(self._M), _vp(self._feat), int(self._feat.stride(0)), self.S,
-                                               _vp(self.texture), _vp(self.counter), _vp(self._winner), self._stream())
-        if rc < 0:
-            raise RuntimeError(f"sgr_texture_atlas failed ({rc}): {_lib.last_error()}")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        call("sgr_texture_atlas", self.device, self.T, self.n, self.s, int(self._verts.shape[0]), ptr(self._verts), ptr(self._faces),
+             ptr(self._points), ptr(self._M), ptr(self._feat), int(self._feat.stride(0)), self.S, ptr(self.texture), ptr(self.counter),
+             ptr(self._winner))
 
     def bake_view(self, fragments, rgb: torch.Tensor, znear: float, zfar: float) -> None:
         """fragments: a pytorch3d-style `Fragments` (or the tuple pix_to_face, zbuf, bary_coords, dists) of ONE image at K = 1,
@@ -150,22 +140,14 @@ class TextureBaker:
         _check(zbuf.dtype == torch.float32 and bary.dtype == torch.float32 and dists.dtype == torch.float32,
                "bake_view: zbuf, bary_coords and dists must be float32")
         sh, sw, sc = (int(x) for x in rgb.stride())
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            rc = lib.sgr_texture_bake_view(W, H, self.view, _vp(p2f), _vp(bary), _vp(zbuf), _vp(dists), float(znear), float(zfar),
-                                           self.T, _vp(self._verts_uv), _vp(rgb), sh, sw, sc, self.S, _vp(self._winner),
-                                           _vp(self.texture), _vp(self.counter), self._stream())
-        if rc < 0:
-            raise RuntimeError(f"sgr_texture_bake_view failed ({rc}): {_lib.last_error()}")
+        call("sgr_texture_bake_view", self.device, W, H, self.view, ptr(p2f), ptr(bary), ptr(zbuf), ptr(dists), float(znear), float(zfar),
+             self.T, ptr(self._verts_uv), ptr(rgb), sh, sw, sc, self.S, ptr(self._winner), ptr(self.texture), ptr(self.counter))
         self.view += 1
 
     def result(self) -> torch.Tensor:
         """texture / counter.clamp(min=1): [S,S,3] float32 (the init image where no view reached a texel)"""
         out = torch.empty_like(self.texture)
-        with torch.cuda.device(self.device):
-            rc = _lib.load().sgr_texture_finalize(self.S, _vp(self.texture), _vp(self.counter), _vp(out), self._stream())
-        if rc < 0:
-            raise RuntimeError(f"sgr_texture_finalize failed ({rc}): {_lib.last_error()}")
+        call("sgr_texture_finalize", self.device, self.S, ptr(self.texture), ptr(self.counter), ptr(out))
         return out
 
 

@@ -23,6 +23,8 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
+from ._call import call, ptr
+
 
 # ---------------------------------------------------------------- loss (sugar_utils/loss_utils.py:17-63)
 def l1_loss(network_output, gt):
@@ -83,28 +85,17 @@ class _Activations(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, scaling, rotation, opacity, sinks):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         if not scaling.is_cuda:
             raise RuntimeError("the fused activations need tensors on a ROCm device; there is no CPU fallback")
         P, dev = scaling.shape[0], scaling.device
         scales, rots, opac = torch.empty_like(scaling), torch.empty_like(rotation), torch.empty_like(opacity)
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.sgr_activations_forward(P, vp(scaling), vp(rotation), vp(opacity), vp(scales), vp(rots), vp(opac),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_activations_forward failed ({rc})")
+        call("sgr_activations_forward", dev, P, ptr(scaling), ptr(rotation), ptr(opacity), ptr(scales), ptr(rots), ptr(opac))
         ctx.save_for_backward(scaling, rotation, opacity)
         ctx.sinks = sinks
         return scales, rots, opac
 
     @staticmethod
     def backward(ctx, g_scales, g_rots, g_opac):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         scaling, rotation, opacity = ctx.saved_tensors
         P, dev = scaling.shape[0], scaling.device
         gs = torch.zeros_like(scaling) if g_scales is None else g_scales.contiguous()
@@ -112,12 +103,8 @@ class _Activations(torch.autograd.Function):
         go = torch.zeros_like(opacity) if g_opac is None else g_opac.contiguous()
         ds, dr, do = ctx.sinks if ctx.sinks is not None else (torch.empty_like(scaling), torch.empty_like(rotation),
                                                              torch.empty_like(opacity))
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.sgr_activations_backward(P, vp(scaling), vp(rotation), vp(opacity), vp(gs), vp(gr), vp(go), vp(ds), vp(dr),
-                                              vp(do), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc < 0:
-            raise RuntimeError(f"sgr_activations_backward failed ({rc})")
+        call("sgr_activations_backward", dev, P, ptr(scaling), ptr(rotation), ptr(opacity), ptr(gs), ptr(gr), ptr(go), ptr(ds), ptr(dr),
+             ptr(do))
         return ds, dr, do, None
 
 
@@ -222,7 +209,8 @@ class FlatAdam:
     def __init__(self, params: GaussianParams, betas=(0.9, 0.999), eps=1e-15):
         import ctypes as C
         from . import _lib
-        self._C, self._lib = C, _lib.load()
+        self._C = C
+        _lib.load()
         self.params = params
         self.betas, self.eps, self.t = betas, eps, 0
         self.exp_avg = torch.zeros_like(params.flat)
@@ -274,38 +262,24 @@ class FlatAdam:
         """The SH half of the step on the CURRENT stream (a trainer may run it on a second stream, next to step_small and the
         geometry half of the next forward).  `means3D` must hold the positions the views were rendered with."""
         C, p = self._C, self.params
-        dev = p.flat.device
-        vp = lambda t: C.c_void_p(t.data_ptr())
         means3D, campos_all, dcolor_all, sh_degree = sh_views
         off = p.offsets["features"]
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            dcol, vstride = _view_rows(dcolor_all)
-            campos_all = campos_all.contiguous()  # (kept referenced until the call is enqueued)
-            rc = self._lib.sgr_sh_adam_from_views_ex(
-                p.P, int(dcolor_all.shape[0]), int(sh_degree), p.M, vp(means3D), vp(campos_all),
-                vp(dcol), int(vstride), C.c_void_p(p.flat.data_ptr() + 4 * off),
-                C.c_void_p(self.exp_avg.data_ptr() + 4 * off), C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * off),
-                p.LRS["features"], p.REST_LR, self.betas[0], self.betas[1], self.eps, self.t, float(grad_scale),
-                C.c_void_p(dmean_extra.data_ptr()) if dmean_extra is not None else None, stream)
-        if rc < 0:
-            raise RuntimeError(f"sgr_sh_adam_from_views failed ({rc})")
+        dcol, vstride = _view_rows(dcolor_all)
+        campos_all = campos_all.contiguous()  # (kept referenced until the call is enqueued)
+        call("sgr_sh_adam_from_views_ex", p.flat.device,
+             p.P, int(dcolor_all.shape[0]), int(sh_degree), p.M, ptr(means3D), ptr(campos_all),
+             ptr(dcol), int(vstride), C.c_void_p(p.flat.data_ptr() + 4 * off),
+             C.c_void_p(self.exp_avg.data_ptr() + 4 * off), C.c_void_p(self.exp_avg_sq.data_ptr() + 4 * off),
+             p.LRS["features"], p.REST_LR, self.betas[0], self.betas[1], self.eps, self.t, float(grad_scale), ptr(dmean_extra))
 
     def step_small(self, grad_scale: float = 1.0, extra=None):
         """Everything but the SH tensor: the 11 other floats per Gaussian (positions included)."""
         self._flat_step(self.params.n_small, self._seg_small, self._n_small, grad_scale, extra)
 
     def _flat_step(self, n_flat, seg, n_seg, grad_scale, extra=None):
-        C, p = self._C, self.params
-        dev = p.flat.device
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = self._lib.sgr_adam_step_ex(n_flat, vp(p.flat), vp(p.flat_grad), vp(self.exp_avg), vp(self.exp_avg_sq), n_seg,
-                                            *seg, self.betas[0], self.betas[1], self.eps, self.t, float(grad_scale),
-                                            vp(extra) if extra is not None else None, 3 * p.P if extra is not None else 0, stream)
-        if rc < 0:
-            raise RuntimeError(f"sgr_adam_step failed ({rc})")
+        p = self.params
+        call("sgr_adam_step_ex", p.flat.device, n_flat, ptr(p.flat), ptr(p.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n_seg,
+             *seg, self.betas[0], self.betas[1], self.eps, self.t, float(grad_scale), ptr(extra), 3 * p.P if extra is not None else 0)
 
 
 def render(params: GaussianParams, cam, bg, rasterizer_cls, settings_cls, sh_degree=3, debug=False, means2D=None,
@@ -343,23 +317,14 @@ def _view_rows(dcolor_all):
 
 def sh_grad_from_views(means3D, campos_all, dcolor_all, sh_degree, out):
     """out[P,M,3] = sum over views of basis(normalize(means3D - campos_v)) (x) dcolor_all[v]  (HIP: sgr_sh_grad_from_views)"""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     if not means3D.is_cuda:
         raise RuntimeError("sh_grad_from_views needs tensors on a ROCm device; there is no CPU fallback")
     V, P = dcolor_all.shape[0], means3D.shape[0]
     M = out.shape[1]
     dev = means3D.device
-    with torch.cuda.device(dev):
-        dcol, vstride = _view_rows(dcolor_all)
-        means3D, campos_all = means3D.contiguous(), campos_all.contiguous()  # (kept referenced until the call is enqueued)
-        rc = lib.sgr_sh_grad_from_views(P, V, int(sh_degree), M, C.c_void_p(means3D.data_ptr()),
-                                        C.c_void_p(campos_all.data_ptr()),
-                                        C.c_void_p(dcol.data_ptr()), int(vstride), C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc < 0:
-        raise RuntimeError(f"sgr_sh_grad_from_views failed ({rc})")
+    dcol, vstride = _view_rows(dcolor_all)
+    means3D, campos_all = means3D.contiguous(), campos_all.contiguous()  # (kept referenced until the call is enqueued)
+    call("sgr_sh_grad_from_views", dev, P, V, int(sh_degree), M, ptr(means3D), ptr(campos_all), ptr(dcol), int(vstride), ptr(out))
     return out
 
 
