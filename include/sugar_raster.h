@@ -219,7 +219,9 @@ int sgr_backward(int P, int D, int M, int64_t R,
 /* sgr_backward in two halves for the compact SH mode (shs given, dL_dsh == NULL), same arguments:
  *   phase 1: accumulator reset + blend backward, then the clamp-masked colour gradients into dL_dcolor[P*3] -- they are
  *            final here, so a view-sharded trainer can start their all-gather;
- *   phase 2: the backward preprocess (every other output; dL_dcolor is not touched again);
+ *   phase 2: the backward preprocess (every other output; dL_dcolor is NOT written).  Phase 1 exists in the compact mode only;
+ *            phase 2 is also accepted with dL_dsh given (the preprocess half over whatever sums the accumulator table holds): such
+ *            a caller gets no colour gradient from it and must hold dL_dcolor from elsewhere -- meant for verification;
  *   phase 0: both, identical to sgr_backward. */
 int sgr_backward_phase(int phase, int P, int D, int M, int64_t R,
                        const float* background, int width, int height,
@@ -247,6 +249,19 @@ typedef struct sgr_backward_opts {
 } sgr_backward_opts;
 #define SGR_BWD_EXACT_ALPHA 2      /* see SGR_FLAG_EXACT_ALPHA */
 #define SGR_BWD_TILE_ORDER_READY 1 /* the forward of this view was given tile_order_out: its launch order is in the image scratch */
+/* The backward preprocess takes a zero-row exit: a rendered Gaussian whose nine blend-backward sums are all zero BY VALUE (most of a
+ * frustum is occluded in any one view) gets its gradient rows written as zeros without its mean, scale, rotation or SH block being
+ * read; the densification statistics count it as before (denom += 1, max_radii2D).  For finite parameters every output equals the
+ * full arithmetic's as a value: a touched row is bit-identical, a zero row may differ in the SIGN of a zero (the full arithmetic
+ * forms -0 in places).  With NaN or inf parameters / coefficients the full arithmetic produces NaN in such a row, the exit 0.
+ * SGR_BWD_DENSE is the verification switch: every rendered row goes through the full arithmetic. */
+#define SGR_BWD_DENSE 8
+/* Self-cleaning accumulator.  The blend backward sums into a private table float[P][16] at sgr_geom_acc_offset_bytes(P) of the
+ * geometry scratch (the forward never writes there), which a backward normally resets first.  With SGR_BWD_ACC_CLEAN the caller
+ * PROMISES that the table is all zero on entry: the reset is skipped, and the backward preprocess (phases 0 and 2: the table's last
+ * reader) stores zeros over every record it found non-zero, so the promise holds again afterwards.  For callers that keep one
+ * geometry scratch across steps (sgr_trainer does; it resets the table itself once, and again after a step that failed half-way). */
+#define SGR_BWD_ACC_CLEAN 4
 int sgr_backward_ex(int phase, int P, int D, int M, int64_t R,
                     const float* background, int width, int height,
                     const float* means3D, const float* shs, const float* colors_precomp,
@@ -303,6 +318,7 @@ size_t sgr_binning_bytes(int64_t R, int width, int height); /* instance list + p
  * 12 floats at geom + sgr_geom_rec_offset() + 48*i:
  *   {x, y, conic.x, conic.y, conic.z, opacity, depth, bitcast(radius), r, g, b, bitcast(clamped bits)} */
 size_t sgr_geom_rec_offset(int P);
+size_t sgr_geom_acc_offset_bytes(int P);                /* float[P][16]: the blend backward's nine sums per Gaussian (SGR_BWD_ACC_CLEAN) */
 size_t sgr_img_final_T_offset(int width, int height);   /* float[W*H] */
 size_t sgr_img_n_contrib_offset(int width, int height); /* uint32[W*H] */
 size_t sgr_img_tile_start_offset(int width, int height);/* uint32[T+1]: tile t owns [start[t], start[t+1]) */
@@ -471,6 +487,10 @@ int sgr_trainer_set_exchange_chunks(sgr_trainer* t, int n);
  * receives the two header copies (word 0: the real num_rendered, word 3: hint miss, word 6: level-1 overflow). */
 int sgr_trainer_forward_valid(sgr_trainer* t, uint32_t* header_out);
 const char* sgr_trainer_last_error(void);
+/* 1 if the next backward of this trainer resets the accumulator table of the geometry scratch itself (at creation, and after a step
+ * that returned an error between the blend backward and the backward preprocess), 0 if the table is known to be zero
+ * (SGR_BWD_ACC_CLEAN: the preprocess kernel of the last step put it back). */
+int sgr_trainer_acc_dirty(sgr_trainer* t);
 /* The gradient exchange of the view-sharded step INSIDE the library (extension; SURVEY.md section 8e: one view per GPU, replicas,
  * "RCCL all-reduce of parameter grads over xGMI"): RCCL is bound at run time (dlopen of librccl.so -- the copy PyTorch has already
  * loaded, if any), one communicator per trainer, collectives on a stream of the library's own.

@@ -39,6 +39,7 @@ SIGNATURES = {
     "sgr_trainer_step": (_i, [_vp, _vp, _i, _vp, _vp]),
     "sgr_trainer_forward_valid": (_i, [_vp, _vp]),
     "sgr_trainer_last_error": (C.c_char_p, []),
+    "sgr_trainer_acc_dirty": (_i, [_vp]),
     "sgr_rccl_unique_id": (_i, [_vp]),
     "sgr_trainer_comm_init": (_i, [_vp, _vp, _i, _i, _vp, _sz]),
     "sgr_trainer_comm_destroy": (_i, [_vp]),
@@ -54,6 +55,7 @@ SIGNATURES = {
     "sgr_img_bytes": (_sz, [_i, _i]),
     "sgr_binning_bytes": (_sz, [_i64, _i, _i]),
     "sgr_geom_rec_offset": (_sz, [_i]),
+    "sgr_geom_acc_offset_bytes": (_sz, [_i]),
     "sgr_img_final_T_offset": (_sz, [_i, _i]),
     "sgr_img_n_contrib_offset": (_sz, [_i, _i]),
     "sgr_img_tile_start_offset": (_sz, [_i, _i]),
@@ -169,7 +171,7 @@ class TrainExchange(C.Structure):
 
 
 SGR_FLAG_RAW_PARAMS, SGR_FLAG_SINGLE_LEVEL_BINNING, SGR_FLAG_SPECULATIVE = 1, 2, 8
-SGR_BWD_TILE_ORDER_READY = 1
+SGR_BWD_TILE_ORDER_READY, SGR_BWD_ACC_CLEAN, SGR_BWD_DENSE = 1, 4, 8
 HDR_R, HDR_HINT_MISS, HDR_L1_OVERFLOW = 0, 3, 6
 
 _lib = None

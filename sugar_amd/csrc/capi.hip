@@ -151,6 +151,7 @@ size_t sgr_geom_bytes(int P) { return sgr_geom_total(P); }
 size_t sgr_img_bytes(int width, int height) { return sgr_img_layout(width, height).total; }
 size_t sgr_binning_bytes(int64_t R, int width, int height) { return sgr_bin_layout(R, sgr_img_layout(width, height).T).total; }
 size_t sgr_geom_rec_offset(int) { return 0; }
+size_t sgr_geom_acc_offset_bytes(int P) { return sgr_geom_acc_offset(P); }
 size_t sgr_img_final_T_offset(int w, int h) { return sgr_img_layout(w, h).final_T; }
 size_t sgr_img_n_contrib_offset(int w, int h) { return sgr_img_layout(w, h).n_contrib; }
 size_t sgr_img_tile_start_offset(int w, int h) { return sgr_img_layout(w, h).tile_start; }
@@ -501,6 +502,14 @@ int sgr_forward_post_job(int width, int height, char* img_buffer, int64_t R, con
     return 0;
 }
 
+}  // extern "C"
+hipError_t sgr_acc_reset(char* geom_buffer, int P, hipStream_t s)
+{
+    SgrStageTimer t(s, SGR_STAGE_FILL);
+    return hipMemsetAsync(geom_buffer + sgr_geom_acc_offset(P), 0, (size_t)P * SGR_ACC_STRIDE * 4, s);
+}
+extern "C" {
+
 static int backward_impl(int phase, int P, int D, int M, int64_t R, const float* background, int width, int height,
                          const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                          float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -524,7 +533,9 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
     // SH gradient is materialised (see sgr_sh_grad_from_views)
     const bool compact = use_sh && !dL_dsh;
     if (!cov3D_precomp && (!dL_dscale || !dL_drot)) return fail(SGR_E_INVALID, "dL_dscale/dL_drot required");
-    if (phase != 0 && !compact) return fail(SGR_E_INVALID, "the two-phase backward is for the compact SH mode");
+    // (phase 2 on its own is well defined in every mode -- the preprocess half over whatever the accumulator table holds, dL_dcolor
+    // left alone --: the tests use it to run both variants of the preprocess kernel over ONE blend backward's sums)
+    if (phase == 1 && !compact) return fail(SGR_E_INVALID, "the two-phase backward is for the compact SH mode");
 
     const ImgLayout IL = sgr_img_layout(width, height);
     const BinLayout BL = sgr_bin_layout(R, IL.T);  // (only point_list, at offset 0 for every R; the masks' offset is read on the device)
@@ -537,8 +548,11 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
 
     // the blend backward accumulates nine sums per Gaussian with atomics into the private acc[P][12] table
     float* acc = reinterpret_cast<float*>(geom_buffer + sgr_geom_acc_offset(P));
+    // SGR_BWD_ACC_CLEAN: the caller promises that the table is all zero on entry (no reset), and the preprocess kernel -- its last
+    // reader in phases 0 and 2 -- stores zeros over every record it found non-zero.  (In phase 1 k_masked_colors is not the last reader.)
+    const bool acc_clean = opts && (opts->flags & SGR_BWD_ACC_CLEAN);
     if (phase != 2) {
-        { SgrStageTimer t(s, SGR_STAGE_FILL); HIP_TRY(hipMemsetAsync(acc, 0, (size_t)P * SGR_ACC_STRIDE * 4, s)); }
+        if (!acc_clean) HIP_TRY(sgr_acc_reset(geom_buffer, P, s));
         if (R > 0) {
             SgrStageTimer t(s, SGR_STAGE_BLEND_BWD);
             // (the forward's per-tile counters are dead by now: their array holds the backward's launch order)
@@ -569,6 +583,8 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
     pb.raw_params = raw_params && !cov3D_precomp;
     pb.sh_dir_elsewhere = sh_dir_elsewhere && use_sh && !dL_dsh;  // (compact SH mode only: see sgr_sh_adam_from_views_ex)
     pb.acc = acc;
+    pb.acc_clean = acc_clean ? 1 : 0;
+    pb.dense = (opts && (opts->flags & SGR_BWD_DENSE)) ? 1 : 0;
     pb.header = reinterpret_cast<const uint32_t*>(img_buffer + IL.header);
     pb.list_cap = (uint32_t)(R > 0xFFFFFFFFll ? 0xFFFFFFFFll : R);
     pb.campos_row = (opts && compact && phase == 0) ? opts->campos_row : nullptr;  // (phase 1 wrote it with the colours)

@@ -482,28 +482,72 @@ __global__ void __launch_bounds__(256) k_depth_keys(PreprocessArgs a)
 #ifndef SGR_PRE_BWD_BLOCKS
 #define SGR_PRE_BWD_BLOCKS 3
 #endif
+// What a lane needs to decide which way its Gaussian goes: the record and the nine sums of the blend backward.
+struct BwdHead { float4 rec0, rec1, rec2, s0, s1; float s2x; };  // {x,y,cx,cy} {cz,opacity,depth,radius} {r,g,b,clamped} {k0,k1,k2,S0} {Sx,Sy,Sxx,Sxy} Syy
+__device__ __forceinline__ void bwd_head_load(const PreprocessBwdArgs& a, int idx, BwdHead& h)
+{
+    const float4* rp4 = reinterpret_cast<const float4*>(a.rec + idx);
+    h.rec0 = rp4[0]; h.rec1 = rp4[1]; h.rec2 = rp4[2];
+    const float4* ap = reinterpret_cast<const float4*>(a.acc + SGR_ACC_STRIDE * (size_t)idx);
+    h.s0 = ap[0]; h.s1 = ap[1];
+    h.s2x = a.acc[SGR_ACC_STRIDE * (size_t)idx + 8];
+}
+// A row the blend backward never reached: all nine sums are zero BY VALUE (-0 counts as zero, a NaN as touched).  Every gradient
+// of such a row is zero (each is a sum of products with one of the nine as a factor), so it takes the zero-row exit below.
+__device__ __forceinline__ bool bwd_touched(const float4 s0, const float4 s1, const float s2x)
+{
+    return !(s0.x == 0.f && s0.y == 0.f && s0.z == 0.f && s0.w == 0.f && s1.x == 0.f && s1.y == 0.f && s1.z == 0.f && s1.w == 0.f &&
+             s2x == 0.f);
+}
+// SGR_BWD_ACC_CLEAN: the last reader of a record puts it back to zero (only the ~10 % the blend backward dirtied are stored to)
+__device__ __forceinline__ void bwd_acc_clean(const PreprocessBwdArgs& a, int idx)
+{
+    float4* ap = reinterpret_cast<float4*>(a.acc + SGR_ACC_STRIDE * (size_t)idx);
+    const float4 z4 = {0.f, 0.f, 0.f, 0.f};
+    ap[0] = z4; ap[1] = z4;
+    a.acc[SGR_ACC_STRIDE * (size_t)idx + 8] = 0.f;
+}
+// Every output row of Gaussian idx as zeros.  `stats`: the row was rendered (radius > 0) and the blend backward left it untouched --
+// the densification statistics count it as the full path would (denom += 1, max_radii2D = max(., radius), grad_accum += |0| is no
+// store); a culled Gaussian or an invalid forward leaves them alone.
 // `stage` (STORE_SH only): this lane's column of its wave's LDS staging panel -- element e of the Gaussian's 48 SH-gradient floats at
 // stage[65 e] -- or NULL for the direct stores (see k_preprocess_bwd below)
-template <bool STORE_SH, int SH>
-__device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, float* __restrict__ stage)
+template <bool STORE_SH>
+__device__ __forceinline__ void bwd_zero_row(const PreprocessBwdArgs& a, int idx, float* __restrict__ stage, bool stats, int radius)
 {
-    const int idx0 = blockIdx.x * 256 + threadIdx.x;
-    if (a.campos_row && idx0 < 3) a.campos_row[idx0] = a.cam_pos[idx0];  // (see sgr_backward_opts)
-    // a sync-free forward whose list outgrew its capacity (or missed its walk hint) did not happen: the gradients are written as
-    // zeros (a caller of the autograd API must never see uninitialised memory) and the densification statistics stay untouched
-    // (denom would count the repeated step twice); the caller repeats the step.  (The three header words travel with the batch
-    // of loads below.)
-    uint32_t hdr_r = 0u, hdr_miss = 0u, hdr_ovf = 0u;
-    if (a.header) { hdr_r = a.header[SGR_HDR_R]; hdr_miss = a.header[SGR_HDR_HINT_MISS]; hdr_ovf = a.header[4 + SGR_B2_HDR_OVERFLOW]; }
-    const bool valid = idx0 < a.P;
-    const int idx = valid ? idx0 : a.P - 1;  // lanes past the end re-read the last Gaussian and store nothing
     const size_t i3 = 3 * (size_t)idx;
-    const float cam_raw = cam_request(a.viewmatrix, a.projmatrix, a.cam_pos);
-    const float4* rp4 = reinterpret_cast<const float4*>(a.rec + idx);
-    const float4 rec0 = rp4[0], rec1 = rp4[1], rec2 = rp4[2];  // {x,y,cx,cy} {cz,opacity,depth,radius} {r,g,b,clamped}
-    const float4* ap = reinterpret_cast<const float4*>(a.acc + SGR_ACC_STRIDE * (size_t)idx);
-    const float4 s0 = ap[0], s1 = ap[1];  // {k0,k1,k2,S0} {Sx,Sy,Sxx,Sxy} {Syy,-,-,-}
-    const float s2x = a.acc[SGR_ACC_STRIDE * (size_t)idx + 8];
+    const int n_sh = a.M * 3;
+    if (a.dL_dmean2D) { a.dL_dmean2D[i3] = 0; a.dL_dmean2D[i3 + 1] = 0; a.dL_dmean2D[i3 + 2] = 0; }
+    if (a.dL_dconic) { float4 z4 = {0, 0, 0, 0}; *reinterpret_cast<float4*>(a.dL_dconic + 4 * (size_t)idx) = z4; }
+    a.dL_dopacity[idx] = 0;
+    if (a.dL_dcolor) { a.dL_dcolor[i3] = 0; a.dL_dcolor[i3 + 1] = 0; a.dL_dcolor[i3 + 2] = 0; }
+    a.dL_dmean3D[i3] = 0; a.dL_dmean3D[i3 + 1] = 0; a.dL_dmean3D[i3 + 2] = 0;
+    if (a.dL_dcov3D) for (int k = 0; k < 6; k++) a.dL_dcov3D[6 * (size_t)idx + k] = 0;
+    if (STORE_SH) {
+        if (stage) {
+#pragma unroll
+            for (int k = 0; k < 48; k++) stage[65 * k] = 0.0f;
+        } else {
+            for (int k = 0; k < n_sh; k++) a.dL_dsh[(size_t)idx * n_sh + k] = 0;
+        }
+    }
+    if (a.dL_dscale) { a.dL_dscale[i3] = 0; a.dL_dscale[i3 + 1] = 0; a.dL_dscale[i3 + 2] = 0; }
+    if (a.dL_drot) { float4 z = {0, 0, 0, 0}; *reinterpret_cast<float4*>(a.dL_drot + 4 * (size_t)idx) = z; }
+    if (stats) {
+        if (a.dens_denom) a.dens_denom[idx] += 1.0f;
+        if (a.dens_max_radii) a.dens_max_radii[idx] = fmaxf(a.dens_max_radii[idx], (float)radius);
+    }
+}
+
+// The full backward of one rendered Gaussian (radius > 0, valid forward).  The mean, scale and rotation are requested here, with
+// the SH block: a zero row never asks for them, and a touched one pays no extra round trip for them.
+template <bool STORE_SH, int SH>
+__device__ __forceinline__ void bwd_full_row(const PreprocessBwdArgs& a, const int idx, const BwdHead& h, const Cam& cam,
+                                             float* __restrict__ stage)
+{
+    const size_t i3 = 3 * (size_t)idx;
+    const float4 rec0 = h.rec0, rec1 = h.rec1, rec2 = h.rec2, s0 = h.s0, s1 = h.s1;
+    const float s2x = h.s2x;
     const V3 mean = {a.means3D[i3], a.means3D[i3 + 1], a.means3D[i3 + 2]};
     float sc[3] = {0, 0, 0}, q[4] = {0, 0, 0, 0};
     float4 q_raw = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -517,33 +561,9 @@ __device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, 
     }
     const int radius = __float_as_int(rec1.w);
     const uint32_t clamped = __float_as_uint(rec2.w);
-    Cam cam;
-    cam_unpack(cam_raw, cam);
-    if (!valid) return;
-    const bool fwd_invalid = hdr_r > a.list_cap || hdr_miss != 0u || hdr_ovf != 0u;  // SGR_FORWARD_INVALID: zero gradients, no statistics
     const float* v = cam.vm;
-
     float dmean[3] = {0, 0, 0}, dcov[6] = {0, 0, 0, 0, 0, 0};
     const int n_sh = a.M * 3;
-    if (fwd_invalid || !(radius > 0)) {
-        if (a.dL_dmean2D) { a.dL_dmean2D[i3] = 0; a.dL_dmean2D[i3 + 1] = 0; a.dL_dmean2D[i3 + 2] = 0; }
-        if (a.dL_dconic) { float4 z4 = {0, 0, 0, 0}; *reinterpret_cast<float4*>(a.dL_dconic + 4 * (size_t)idx) = z4; }
-        a.dL_dopacity[idx] = 0;
-        if (a.dL_dcolor) { a.dL_dcolor[i3] = 0; a.dL_dcolor[i3 + 1] = 0; a.dL_dcolor[i3 + 2] = 0; }
-        a.dL_dmean3D[i3] = 0; a.dL_dmean3D[i3 + 1] = 0; a.dL_dmean3D[i3 + 2] = 0;
-        if (a.dL_dcov3D) for (int k = 0; k < 6; k++) a.dL_dcov3D[6 * (size_t)idx + k] = 0;
-        if (STORE_SH) {
-            if (stage) {
-#pragma unroll
-                for (int k = 0; k < 48; k++) stage[65 * k] = 0.0f;
-            } else {
-                for (int k = 0; k < n_sh; k++) a.dL_dsh[(size_t)idx * n_sh + k] = 0;
-            }
-        }
-        if (a.dL_dscale) { a.dL_dscale[i3] = 0; a.dL_dscale[i3 + 1] = 0; a.dL_dscale[i3 + 2] = 0; }
-        if (a.dL_drot) { float4 z = {0, 0, 0, 0}; *reinterpret_cast<float4*>(a.dL_drot + 4 * (size_t)idx) = z; }
-        return;
-    }
     float sh[48];
     if (SH != 2) load_sh<48, SH == 0>(a.shs, idx, a.M, sh);
     if (!a.cov3D_precomp) {
@@ -771,6 +791,60 @@ __device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, 
     }
 }
 
+// One lane per Gaussian.  Everything whose address is known at entry and that EVERY row needs (the record, the nine sums, the
+// camera, the header) is requested in one batch; then the row goes one of three ways: zeros without statistics (culled, or the
+// forward was invalid), zeros with statistics (rendered, but the blend backward never reached it: most of a frustum is occluded in
+// any one view), or the full backward.  a.dense (SGR_BWD_DENSE) sends every rendered row through the full backward.
+template <bool STORE_SH, int SH>
+__device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, float* __restrict__ stage, const int idx0)
+{
+    if (a.campos_row && idx0 < 3) a.campos_row[idx0] = a.cam_pos[idx0];  // (see sgr_backward_opts)
+    // a sync-free forward whose list outgrew its capacity (or missed its walk hint) did not happen: the gradients are written as
+    // zeros (a caller of the autograd API must never see uninitialised memory) and the densification statistics stay untouched
+    // (denom would count the repeated step twice); the caller repeats the step.  (The three header words travel with the batch
+    // of loads below.)
+    uint32_t hdr_r = 0u, hdr_miss = 0u, hdr_ovf = 0u;
+    if (a.header) { hdr_r = a.header[SGR_HDR_R]; hdr_miss = a.header[SGR_HDR_HINT_MISS]; hdr_ovf = a.header[4 + SGR_B2_HDR_OVERFLOW]; }
+    const bool valid = idx0 < a.P;
+    const int idx = valid ? idx0 : a.P - 1;  // lanes past the end re-read the last Gaussian and store nothing
+    const float cam_raw = cam_request(a.viewmatrix, a.projmatrix, a.cam_pos);
+    BwdHead h;
+    bwd_head_load(a, idx, h);
+    Cam cam;
+    cam_unpack(cam_raw, cam);
+    if (a.acc_clean) {
+        // SGR_BWD_ACC_CLEAN.  Where the blend backward reached few rows (a tenth of them on the metric scene) each lane puts its own
+        // record back.  Where it reached most (a bound, opaque surface: 99 %) that would be three strided partial stores per lane over
+        // the whole table: a wave that finds half of its 64 records dirty zeroes its 4 KB of the table as ONE contiguous stream
+        // instead (every lane's record has been read by now: the ballot below waits for all of them).
+        const bool dirty = valid && bwd_touched(h.s0, h.s1, h.s2x);
+        const unsigned long long m = __ballot(dirty);
+        if (__popcll(m) >= 32) {  // (wave-uniform)
+            const int lane = threadIdx.x & 63;
+            const long long row0 = (long long)idx0 - lane;  // the wave's first Gaussian
+            float4* w4 = reinterpret_cast<float4*>(a.acc + SGR_ACC_STRIDE * (size_t)row0);
+            const float4 z4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int j = i * 64 + lane;  // float4 index in the wave's 64 records of 4 float4
+                if (row0 + (j >> 2) < (long long)a.P) w4[j] = z4;
+            }
+        } else if (dirty) {
+            bwd_acc_clean(a, idx);
+        }
+    }
+    if (!valid) return;
+    const bool fwd_invalid = hdr_r > a.list_cap || hdr_miss != 0u || hdr_ovf != 0u;  // SGR_FORWARD_INVALID: zero gradients, no statistics
+    const int radius = __float_as_int(h.rec1.w);
+    const bool touched = bwd_touched(h.s0, h.s1, h.s2x);
+    const bool rendered = !fwd_invalid && radius > 0;
+    if (!rendered || !(touched || a.dense)) {
+        bwd_zero_row<STORE_SH>(a, idx, stage, rendered, radius);
+        return;
+    }
+    bwd_full_row<STORE_SH, SH>(a, idx, h, cam, stage);
+}
+
 template <bool STORE_SH, int SH>
 __global__ void __launch_bounds__(256, SGR_PRE_BWD_BLOCKS) k_preprocess_bwd(PreprocessBwdArgs a)
 {
@@ -782,7 +856,7 @@ __global__ void __launch_bounds__(256, SGR_PRE_BWD_BLOCKS) k_preprocess_bwd(Prep
     const bool staged = STORE_SH && a.M == 16 && (((uintptr_t)a.dL_dsh) & 15) == 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* panel = s_stage + (STORE_SH ? wave * (48 * 65) : 0);
-    preprocess_bwd_lane<STORE_SH, SH>(a, staged ? panel + lane : nullptr);
+    preprocess_bwd_lane<STORE_SH, SH>(a, staged ? panel + lane : nullptr, blockIdx.x * 256 + threadIdx.x);
     if (STORE_SH && staged) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();

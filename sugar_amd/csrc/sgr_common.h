@@ -17,7 +17,7 @@
 
 // ---- private scratch layouts -----------------------------------------------------------------
 // geom  : [ GeomRec rec[P] | acc f32[P][16] | sort scratch ]   48 B / Gaussian record (AoS: one gather = 1-2 lines),
-//           the backward's per-Gaussian accumulator (zeroed by each backward), and the depth sort's ping-pong
+//           the backward's per-Gaussian accumulator (zeroed by each backward, or kept zero between backwards: SGR_BWD_ACC_CLEAN), and the depth sort's ping-pong
 //           key/value arrays (the sorted Gaussian order stays there for the backward-free forward only)
 // img   : [ final_T f32[WH] | n_contrib u32[WH] | tile_start u32[T+1] | tile_count u32[T] |
 //           tile_maxc u32[T] | tile_walked u32[T] | blk_nb u32[4T] | header u32[8] | blk_hist u32[n_blocks][T] ]
@@ -38,6 +38,8 @@ size_t sgr_sort_scratch_bytes(int P);  // binning.hip
                            // (one record = one half cache line: the nine atomics of a (block, Gaussian) pair coalesce)
 static inline size_t sgr_geom_sort_offset(int P) { return sgr_geom_acc_offset(P) + sgr_align((size_t)(P > 0 ? P : 1) * SGR_ACC_STRIDE * 4); }
 size_t sgr_sort_rects_offset(int P);    // binning.hip: offset of the packed rectangles inside the sort scratch
+// reset of the backward's accumulator table inside a geometry scratch (capi.hip; timed as SGR_STAGE_FILL): hipSuccess or the error
+hipError_t sgr_acc_reset(char* geom_buffer, int P, hipStream_t s);
 static inline size_t sgr_geom_total(int P) { return sgr_geom_sort_offset(P) + sgr_sort_scratch_bytes(P); }
 
 struct ImgLayout {
@@ -160,7 +162,9 @@ struct PreprocessBwdArgs {
     float* campos_row;  // compact mode: receives the camera centre (the row behind the colour gradients in a send buffer) or NULL
     float* dens_max_radii; float* dens_accum; float* dens_denom;  // fused densification statistics (sgr_backward_opts) or NULL
     const uint32_t* header; uint32_t list_cap;  // the forward's device header (or NULL): an INVALID sync-free forward makes the kernel a no-op
-    const float* acc;  // [P][SGR_ACC_STRIDE] sums from the blend backward: {dcol r,g,b, S0, Sx, Sy, Sxx, Sxy, Syy, pad x3}
+    float* acc;  // [P][SGR_ACC_STRIDE] sums from the blend backward: {dcol r,g,b, S0, Sx, Sy, Sxx, Sxy, Syy, pad x3}
+    int acc_clean;  // SGR_BWD_ACC_CLEAN: store zeros over every record found non-zero, after reading it (this kernel is its last reader)
+    int dense;      // SGR_BWD_DENSE: every rendered row takes the full backward (no zero-row exit)
     float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolor;  // written here from acc
     float* dL_dmean3D; float* dL_dcov3D; float* dL_dsh; float* dL_dscale; float* dL_drot;
 };

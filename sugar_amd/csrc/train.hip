@@ -83,6 +83,7 @@ struct sgr_trainer {
     double last_wait_ms = 0.0;    // what the last sgr_trainer_step_exchange spent waiting for the forward's header
     hipEvent_t hdr_event = nullptr;
     bool have_forward = false;
+    bool acc_dirty = true;      // the geometry scratch's accumulator table may hold non-zero records: the next backward resets it
     bool defer_post = false;    // the post-blend bookkeeping rides in the loss forward kernel (needs a device-mapped header_host)
     int64_t R = 0;              // what the last forward returned (= the capacity)
     long long seg_begin[4], seg_end[4];
@@ -145,6 +146,8 @@ int sgr_trainer_set_binning(sgr_trainer* t, char* binning, size_t bytes, int64_t
     t->c.binning = binning; t->c.binning_bytes = bytes; t->c.binning_capacity = capacity;
     return 0;
 }
+
+int sgr_trainer_acc_dirty(sgr_trainer* t) { return (t && !t->acc_dirty) ? 0 : 1; }
 
 int sgr_trainer_forward_valid(sgr_trainer* t, uint32_t* header_out)
 {
@@ -209,20 +212,30 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
         if (!t->have_forward) return tfail(SGR_E_INVALID, "sgr_trainer_step: backward before any forward");
         // (camera centre: the row behind the colours; the launch order: sorted by the job that rode in the loss kernel, or by the
         // forward itself when the view keeps the order)
+        // (SGR_BWD_ACC_CLEAN: the accumulator table is zero between steps -- the preprocess kernel puts the few records the blend
+        // backward dirtied back -- so no step resets its 64 B per Gaussian; see acc_dirty below)
         sgr_backward_opts bo = {c.max_radii2D, c.grad_accum, c.denom, c.colors + 3 * (size_t)P,
-                                (t->defer_post || v->tile_order_out) ? SGR_BWD_TILE_ORDER_READY : 0};
+                                ((t->defer_post || v->tile_order_out) ? SGR_BWD_TILE_ORDER_READY : 0) | SGR_BWD_ACC_CLEAN};
         // compact SH mode (dL_dsh == NULL), raw-parameter gradients straight into the flat gradient buffer.  Both halves asked
         // for at once (no collective to start in between): ONE pass, the preprocess kernel writes the masked colour gradients
         // itself (the split costs a 23 us kernel of its own)
         const int first = (phases & 3) == 3 ? 0 : ((phases & 1) ? 1 : 2);
         const int last = (phases & 3) == 3 ? 0 : ((phases & 2) ? 2 : 1);
         for (int ph = first; ph <= last; ph++) {
+            if (ph != 2) {
+                // the table is dirty from here until the preprocess half has been enqueued: a step that returns an error in between
+                // costs the next one a reset, not wrong gradients
+                if (t->acc_dirty && sgr_acc_reset(c.geom, P, s) != hipSuccess)
+                    return tfail(SGR_E_HIP, "sgr_trainer_step: accumulator reset failed");
+                t->acc_dirty = true;
+            }
             const int rc = sgr_backward_ex(ph | SGR_MODE_RAW_PARAMS, P, c.D, c.M, t->R, c.background, W, H, means3D, shs, nullptr, scal,
                                            1.0f, rot, nullptr, v->viewmatrix, v->projmatrix, v->campos, v->tan_fovx, v->tan_fovy,
                                            c.radii, c.geom, c.binning, c.img, c.grad_image, c.dL_dmean2D, nullptr,
                                            grad + c.off_opacity, c.colors, grad + c.off_xyz, nullptr, nullptr, grad + c.off_scaling,
                                            grad + c.off_rotation, 0, stream, &bo);
             if (rc < 0) return tfail(rc, std::string("backward: ") + sgr_last_error());
+            if (ph != 1) t->acc_dirty = false;
         }
     }
     if (phases & 12) {
