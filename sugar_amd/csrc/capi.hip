@@ -546,7 +546,7 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
     const uint32_t* blk_nb = reinterpret_cast<const uint32_t*>(img_buffer + IL.blk_nb);
     const uint32_t* point_list = reinterpret_cast<const uint32_t*>(binning_buffer + BL.point_list);
 
-    // the blend backward accumulates nine sums per Gaussian with atomics into the private acc[P][12] table
+    // the blend backward accumulates nine sums per Gaussian with atomics into the private acc[P][16] table (SGR_ACC_STRIDE)
     float* acc = reinterpret_cast<float*>(geom_buffer + sgr_geom_acc_offset(P));
     // SGR_BWD_ACC_CLEAN: the caller promises that the table is all zero on entry (no reset), and the preprocess kernel -- its last
     // reader in phases 0 and 2 -- stores zeros over every record it found non-zero.  (In phase 1 k_masked_colors is not the last reader.)

@@ -686,6 +686,9 @@ __device__ __forceinline__ void bwd_full_row(const PreprocessBwdArgs& a, const i
 #pragma unroll
                 for (int e = 0; e < 48; e++) stage[65 * e] = (e / 3) < n_act ? b[e / 3] * dLm[e % 3] : 0.0f;
             } else if (n_sh == 48 && ((uintptr_t)dst & 15) == 0) {
+                // (not reachable from k_preprocess_bwd: M == 16 with an aligned dL_dsh is exactly its condition for staging.  Kept:
+                // without it the register allocation of both STORE_SH kernels changes -- 152 -> 154 VGPRs, ~1 300 instructions
+                // move --, which wants a timing run of its own)
                 float4* d4 = reinterpret_cast<float4*>(dst);
 #pragma unroll
                 for (int i = 0; i < 12; i++) {

@@ -1,6 +1,8 @@
 """Helpers shared by the parity tests: run the CPU oracle and the HIP path on the same seeded inputs."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -106,3 +108,104 @@ def rel_stats(a, b, floor_frac=1e-3):
     nrm = np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
     return dict(max_rel=float(rel.max()) if rel.size else 0.0, frac_gt_1e4=float((rel > 1e-4).mean()) if rel.size else 0.0,
                 norm_rel=float(nrm), max_abs=float(np.abs(a - b).max()) if a.size else 0.0, scale=float(scale))
+
+
+def grad_image(W, H):
+    return np.random.default_rng(0).standard_normal((3, H, W)).astype(np.float32)
+
+
+MODE_RAW, MODE_SH_DIR_ELSEWHERE = 4, 8   # SGR_MODE_RAW_PARAMS, SGR_MODE_SH_DIR_ELSEWHERE
+
+
+class Run:
+    """One forward through the C ABI, and backwards over its scratch (sgr_backward_ex with flags).
+
+    raw: the raw 3DGS parameters (log scale, un-normalised quaternion, opacity logit), derived from the activated scene -- or, with
+    raw_given, the scene's fields hold them already.  colors / cov: colors_precomp [P,3] / cov3D_precomp [P,6] instead of the SH
+    coefficients / of scales and rotations.  The image size is the camera's."""
+
+    def __init__(self, scene, cam, bg, raw, *, raw_given=False, D=3, M=16, colors=None, cov=None, scale_modifier=1.0, device="cuda:0"):
+        from sugar_amd import _lib
+        from sugar_amd.diff_gaussian_rasterization import _Scratch
+        self.L, self.lib = _lib, _lib.load()
+        self.dev = dev = torch.device(device)
+        self.P = P = scene.means3D.shape[0]
+        self.W, self.H = W, H = cam.image_width, cam.image_height
+        self.raw, self.D, self.M, self.mod = bool(raw), int(D), int(M), float(scale_modifier)
+        f = lambda t: None if t is None else torch.as_tensor(t).to(dev).float().contiguous()
+        self.means, self.shs = f(scene.means3D), (f(scene.shs[:, :M]) if colors is None else None)
+        self.colors, self.cov = f(colors), f(cov)
+        if raw and not raw_given:  # the raw 3DGS parameters: log scale, un-normalised quaternion, opacity logit
+            self.scales, self.rots = f(scene.scales.log()), f(scene.rotations * 2.5)
+            self.opac = f(torch.logit(scene.opacities))
+        else:
+            self.scales, self.rots, self.opac = f(scene.scales), f(scene.rotations), f(scene.opacities)
+        if cov is not None:
+            self.scales = self.rots = None
+        self.bg, self.vm, self.pm, self.cp = f(bg), f(cam.viewmatrix), f(cam.projmatrix), f(cam.campos)
+        self.tx, self.ty = float(cam.tanfovx), float(cam.tanfovy)
+        self.color = torch.empty(3, H, W, device=dev)
+        self.radii = torch.empty(P, dtype=torch.int32, device=dev)
+        self.dpix = torch.as_tensor(grad_image(W, H)).to(dev)
+        sc = _Scratch(dev)
+        opts = _lib.ForwardOpts(0, _lib.SGR_FLAG_RAW_PARAMS if raw else 0, None, None, None, None, 0.0, 0, None, None, None)
+        p = self.ptr
+        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self.R = self.lib.sgr_forward_ex(sc.cb("geom"), None, sc.cb("binning"), None, sc.cb("img"), None, P, self.D, self.M, p(self.bg),
+                                         W, H, p(self.means), p(self.shs), p(self.colors), p(self.opac), p(self.scales), self.mod,
+                                         p(self.rots), p(self.cov), p(self.vm), p(self.pm), p(self.cp), self.tx, self.ty, 0,
+                                         p(self.color), p(self.radii), 0, self.stream, C.byref(opts))
+        assert self.R >= 0, _lib.last_error()
+        self.scratch = sc.release()
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def acc(self):
+        """the accumulator table float[P][16] inside the geometry scratch (a view: writable)"""
+        o = self.lib.sgr_geom_acc_offset_bytes(self.P)
+        return self.scratch["geom"][o:o + self.P * 64].view(torch.float32).view(self.P, 16)
+
+    def record(self):
+        """the forward's 48-byte record of every Gaussian, as float32 [P,12] on the host (columns: REC_* above)"""
+        torch.cuda.synchronize()
+        return self.scratch["geom"][: self.P * 48].cpu().numpy().view(np.float32).reshape(self.P, 12)
+
+    def backward(self, phase, store_sh, flags=0, stats=True, *, mode=0, dpix=None, dens0=None, intermediates=True, sh_offset=0):
+        """-> dict of device tensors: every output of the call, and the three densification statistics (going in: dens0 =
+        (max_radii, accum, denom), or zeros with max_radii at 2).  mode: further SGR_MODE_* bits; intermediates=False passes NULL
+        for dL_dmean2D and dL_dconic; sh_offset: dL_dsh starts that many floats past a 256-byte boundary."""
+        dev, P = self.dev, self.P
+        nan = lambda *s: torch.full(s, float("nan"), device=dev)
+        out = dict(opacity=nan(P), color=nan(P, 3), mean3D=nan(P, 3))
+        if intermediates:
+            out.update(mean2D=nan(P, 3), conic=nan(P, 4))
+        if self.cov is None:
+            out.update(scale=nan(P, 3), rot=nan(P, 4))
+        else:
+            out["cov3D"] = nan(P, 6)
+        if store_sh:
+            self._sh_buf = nan(P * self.M * 3 + sh_offset)
+            out["sh"] = self._sh_buf[sh_offset:].view(P, self.M, 3)
+        p = self.ptr
+        if dens0 is None:
+            dens = [torch.zeros(P, device=dev) for _ in range(3)]
+            dens[0].fill_(2.0)  # max_radii2D starts above the smallest radii: the maximum must keep it
+        else:
+            dens = [torch.as_tensor(t).to(dev).float().clone() for t in dens0]
+        bo = self.L.BackwardOpts(*([t.data_ptr() for t in dens] if stats else [None] * 3), None, int(flags))
+        g, b, i = (self.scratch[k] for k in ("geom", "binning", "img"))
+        dpix = self.dpix if dpix is None else dpix
+        rc = self.lib.sgr_backward_ex(phase | mode | (MODE_RAW if self.raw else 0), P, self.D, self.M, self.R, p(self.bg), self.W, self.H,
+                                      p(self.means), p(self.shs), p(self.colors), p(self.scales), self.mod, p(self.rots), p(self.cov),
+                                      p(self.vm), p(self.pm), p(self.cp), self.tx, self.ty, p(self.radii), p(g), p(b), p(i), p(dpix),
+                                      p(out.get("mean2D")), p(out.get("conic")), p(out["opacity"]), p(out["color"]), p(out["mean3D"]),
+                                      p(out.get("cov3D")), p(out.get("sh")), p(out.get("scale")), p(out.get("rot")), 0, self.stream,
+                                      C.byref(bo))
+        assert rc >= 0, self.L.last_error()
+        torch.cuda.synchronize()
+        if phase == 2:
+            del out["color"]  # (written by phase 1)
+        out.update(max_radii=dens[0], accum=dens[1], denom=dens[2])
+        return out

@@ -6,7 +6,6 @@ Scenes: synthetic config1 at 256x256 with P = 60 013 (about a fifth of the visib
 any 256 K), 10 000 (most rows touched) and 37 (less than one wave), and one constructed scene of 4 096 + 64 + 5 Gaussians: a
 whole workgroup tile of rendered-but-transparent Gaussians (opacity 1e-3 < 1/255: never blended), then 64 that all contribute.
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -22,7 +21,6 @@ DEV = "cuda:0"
 W = H = 256
 SIZES = (60013, 10000, 37)
 CAMS = (0, 3)
-MODE_RAW = 4   # SGR_MODE_RAW_PARAMS
 N_TILE = 4096  # Gaussians of the constructed scene's transparent run
 N_SUB = 8      # transparent Gaussians of the constructed sub-wave scene
 
@@ -50,8 +48,8 @@ def _scene(P):
     return scene._replace(means3D=means, scales=scales, opacities=opac), cams, bg
 
 
-def _grad_image():
-    return np.random.default_rng(0).standard_normal((3, H, W)).astype(np.float32)
+_grad_image = lambda: pu.grad_image(W, H)
+_Run = pu.Run   # one forward through the C ABI, and backwards over its scratch (shared with tests/test_gpu_preprocess_bwd_rows.py)
 
 
 @functools.lru_cache(maxsize=None)
@@ -66,68 +64,6 @@ def _oracle(P, cam_i):
         touched |= (gr[k].reshape(n, -1) != 0).any(axis=1)
     vis = st["radii"] > 0
     return st, gr, vis, vis & ~touched
-
-
-class _Run:
-    """One forward through the C ABI, and backwards over its scratch (sgr_backward_ex with flags)."""
-
-    def __init__(self, scene, cam, bg, raw):
-        from sugar_amd import _lib
-        from sugar_amd.diff_gaussian_rasterization import _Scratch
-        self.L, self.lib = _lib, _lib.load()
-        dev = torch.device(DEV)
-        self.P = P = scene.means3D.shape[0]
-        self.raw = bool(raw)
-        f = lambda t: t.to(dev).float().contiguous()
-        self.means, self.shs = f(scene.means3D), f(scene.shs)
-        if raw:  # the raw 3DGS parameters: log scale, un-normalised quaternion, opacity logit
-            self.scales, self.rots = f(scene.scales.log()), f(scene.rotations * 2.5)
-            self.opac = f(torch.logit(scene.opacities))
-        else:
-            self.scales, self.rots, self.opac = f(scene.scales), f(scene.rotations), f(scene.opacities)
-        self.bg, self.vm, self.pm, self.cp = f(bg), f(cam.viewmatrix), f(cam.projmatrix), f(cam.campos)
-        self.tx, self.ty = float(cam.tanfovx), float(cam.tanfovy)
-        self.color = torch.empty(3, H, W, device=dev)
-        self.radii = torch.empty(P, dtype=torch.int32, device=dev)
-        self.dpix = torch.as_tensor(_grad_image()).to(dev)
-        sc = _Scratch(dev)
-        opts = _lib.ForwardOpts(0, _lib.SGR_FLAG_RAW_PARAMS if raw else 0, None, None, None, None, 0.0, 0, None, None, None)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self.R = self.lib.sgr_forward_ex(sc.cb("geom"), None, sc.cb("binning"), None, sc.cb("img"), None, P, 3, 16, p(self.bg), W, H,
-                                         p(self.means), p(self.shs), None, p(self.opac), p(self.scales), 1.0, p(self.rots), None,
-                                         p(self.vm), p(self.pm), p(self.cp), self.tx, self.ty, 0, p(self.color), p(self.radii), 0,
-                                         self.stream, C.byref(opts))
-        assert self.R >= 0, _lib.last_error()
-        self.scratch = sc.release()
-
-    def acc(self):
-        o = self.lib.sgr_geom_acc_offset_bytes(self.P)
-        return self.scratch["geom"][o:o + self.P * 64].view(torch.float32).view(self.P, 16)
-
-    def backward(self, phase, store_sh, flags=0, stats=True):
-        """-> dict of device tensors: every output of the call, and the three densification statistics (fresh zeros going in)"""
-        dev, P = torch.device(DEV), self.P
-        nan = lambda *s: torch.full(s, float("nan"), device=dev)
-        out = dict(mean2D=nan(P, 3), conic=nan(P, 4), opacity=nan(P), color=nan(P, 3), mean3D=nan(P, 3), scale=nan(P, 3), rot=nan(P, 4))
-        if store_sh:
-            out["sh"] = nan(P, 16, 3)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        dens = [torch.zeros(P, device=dev) for _ in range(3)]
-        dens[0].fill_(2.0)  # max_radii2D starts above the smallest radii: the maximum must keep it
-        bo = self.L.BackwardOpts(*([t.data_ptr() for t in dens] if stats else [None] * 3), None, int(flags))
-        g, b, i = (self.scratch[k] for k in ("geom", "binning", "img"))
-        rc = self.lib.sgr_backward_ex(phase | (MODE_RAW if self.raw else 0), P, 3, 16, self.R, p(self.bg), W, H, p(self.means),
-                                      p(self.shs), None, p(self.scales), 1.0, p(self.rots), None, p(self.vm), p(self.pm), p(self.cp),
-                                      self.tx, self.ty, p(self.radii), p(g), p(b), p(i), p(self.dpix), p(out["mean2D"]),
-                                      p(out["conic"]), p(out["opacity"]), p(out["color"]), p(out["mean3D"]), None,
-                                      p(out["sh"]) if store_sh else None, p(out["scale"]), p(out["rot"]), 0, self.stream, C.byref(bo))
-        assert rc >= 0, self.L.last_error()
-        torch.cuda.synchronize()
-        if phase == 2:
-            del out["color"]  # (written by phase 1)
-        out.update(max_radii=dens[0], accum=dens[1], denom=dens[2])
-        return out
 
 
 ORACLE_NAMES = dict(mean2D="dL_dmeans2D", opacity="dL_dopacity", mean3D="dL_dmeans3D", scale="dL_dscales", rot="dL_drotations",
