@@ -688,6 +688,30 @@ int sgr_texture_bake_view(int width, int height, int view, const int64_t* pix_to
                           float* texture, float* counter, void* stream);
 int sgr_texture_finalize(int S, const float* texture, const float* counter, float* out, void* stream);
 
+/* ---- shading of the UV-textured refined mesh: SoftPhongShader(AmbientLights) over a TexturesUV, metrics.py:260-300, 370-372 ------------
+ * (csrc/mesh_shade.hip; added under ABI version 4, additive).  One launch, one lane per pixel, no LDS, no atomics, no host synchronisation.
+ * sgr_shade_texture_uv: the hard fragments of ONE view of ONE mesh -- pix_to_face[H,W,K] (int64; negative = empty slot; a covered slot
+ *   names face pix_to_face - face_index_base), bary[H,W,K,3], zbuf[H,W,K], dists[H,W,K], 1 <= K <= 16 -- shaded to rgba[H,W,4] (16-byte
+ *   aligned).  faces_uvs[F,3] (int64) index verts_uvs[n_uv,2]; texture[TH,TW,3] is the map AS STORED: the kernel reads row TH-1-iy in
+ *   place where pytorch3d samples row iy of a flipped copy.  A face index outside [0, F) or a UV index outside [0, n_uv) gives NaN in
+ *   all four channels of that pixel, never an out-of-bounds access.  ambient3 / background3: three HOST floats each.
+ *   Per covered slot, every operation individually rounded (-ffp-contract=off), in this order:
+ *     u = b0*u0; u += b1*u1; u += b2*u2 (v alike); g = u*2 - 1;
+ *     x = align_corners ? ((g+1)/2)*(size-1) : ((g+1)*size-1)/2, clamped to [0, size-1] (padding_mode 'border'; size = TW for u, TH for v);
+ *     bilinear == 0: texel (nearbyint(y), nearbyint(x)), half to even;
+ *     bilinear != 0: corners (y0, x0) = floor, +1: nw*(x1-x)(y1-y) + ne*(x-x0)(y1-y) + sw*(x1-x)(y-y0) + se*(x-x0)(y-y0), a corner
+ *       outside the map adds 0;
+ *     colour = ambient * texel.
+ *   Then softmax_rgb_blend (pytorch3d/renderer/blending.py): prob = sigmoid(-dists/sigma) (0 in an empty slot), alpha = prod(1 - prob),
+ *     z_inv = (zfar - zbuf)/(zfar - znear) (0 in an empty slot), z_max = max(max_k z_inv, 1e-10), w = prob * exp((z_inv - z_max)/gamma),
+ *     delta = max(exp((1e-10 - z_max)/gamma), 1e-10), rgb = (sum_k w colour + delta background) / (sum_k w + delta), A = 1 - alpha.
+ *   A pixel with no covered slot comes out as (background, 0). */
+int sgr_shade_texture_uv(int width, int height, int K, int64_t face_index_base, const int64_t* pix_to_face, const float* bary,
+                         const float* zbuf, const float* dists, int64_t F, const int64_t* faces_uvs, int64_t n_uv,
+                         const float* verts_uvs, const float* texture, int TH, int TW, int bilinear, int align_corners,
+                         const float* ambient3, const float* background3, float sigma, float gamma, float znear, float zfar,
+                         float* rgba, void* stream);
+
 /* ---- the refine stage's mesh binding: SuGaR.points / .scaling / .quaternions of a model bound to a surface mesh ------------------------
  * (csrc/mesh_bind.hip; sugar_scene/sugar_model.py:383-479, the `not editable` branch; added under ABI version 4, additive).
  * F faces, n Gaussians per face, V vertices; Gaussian g = f * n + k.  verts[V,3], faces[F,3] (int32; a vertex index outside [0, V) gives

@@ -104,6 +104,8 @@ SIGNATURES = {
     "sgr_texture_atlas": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "sgr_texture_bake_view": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "sgr_texture_finalize": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "sgr_shade_texture_uv": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _f, _f,
+                                  _vp, _vp]),
     "sgr_mesh_bind_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgr_mesh_bind_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgr_normal_consistency_scratch_bytes": (_sz, []),

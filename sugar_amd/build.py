@@ -28,6 +28,7 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],  # bit-exact with oracle/mesh_rasterizer.c
     "texture.hip": ["-ffp-contract=off"],      # the texel arithmetic of the reference's individually rounded tensor ops
+    "mesh_shade.hip": ["-ffp-contract=off"],   # the shader restates the stand-in SoftPhongShader's individually rounded tensor ops
     "mesh_bind.hip": ["-ffp-contract=off"],    # the binding restates the reference's individually rounded tensor arithmetic
     "marching_cubes.hip": ["-ffp-contract=off"],  # bit-identical with the serial restatement in tests/mc_restatement.py
     "mesh_decimate.hip": ["-ffp-contract=off"],   # bit-identical with the serial restatement in tests/decimate_restatement.py

@@ -3,7 +3,8 @@
 (blur_radius = 0) z-buffer the level-set sampler reads (sugar_scene/sugar_model.py:1880-1893,1927-1928,1966) on the HIP kernel
 of this package (sgr_rasterize_meshes).  Shading is the subset the texture baking of the refined mesh runs
 (sugar_model.py:2607-2661): `AmbientLights`, `BlendParams` / `softmax_rgb_blend` (blending.py), and a `MeshRenderer` /
-`SoftPhongShader` for ambient lights over `TexturesUV` with nearest sampling (mesh/shader.py, plain torch)."""
+`SoftPhongShader` for ambient lights over `TexturesUV` with nearest sampling (mesh/shader.py, plain torch); bilinear sampling on a ROCm
+device without gradients -- how metrics.py:289-300 draws the refined mesh's .obj -- runs on the HIP kernel of sugar_amd.mesh_render."""
 import torch
 
 from .._placeholder import out_of_scope

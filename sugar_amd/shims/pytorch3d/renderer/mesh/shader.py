@@ -4,7 +4,9 @@
 `shader.py`, `shading.py`, `textures.py` (TexturesUV.sample_textures) and `ops/interp_face_attrs.py` (the CPU path,
 interpolate_face_attributes_python); PARITY-UNPINNED against pytorch3d itself.  Other lights or sampling modes raise
 NotImplementedError.  Plain torch: this is the CPU path the fixtures are written with; the product bakes textures with the HIP
-kernels of sugar_amd.texture instead."""
+kernels of sugar_amd.texture instead.  The one call the torch path does not serve -- `sampling_mode='bilinear'` (the default of the
+`TexturesUV` that `load_objs_as_meshes` builds) on a ROCm device with no gradient wanted, what metrics.py:289-300, 372 runs -- goes to
+the HIP shading kernel of sugar_amd.mesh_render, view by view.  Everything the torch path served before keeps it."""
 from __future__ import annotations
 
 import torch
@@ -48,6 +50,51 @@ def sample_textures_uv(textures, fragments) -> torch.Tensor:
     return texels.reshape(N, K, C, H_out, W_out).permute(0, 3, 4, 1, 2)
 
 
+def _takes_hip_path(fragments, textures, lights) -> bool:
+    """bilinear sampling on a ROCm device with nothing to differentiate: exactly the call `sample_textures_uv` raises for"""
+    if getattr(textures, "sampling_mode", None) != "bilinear" or not fragments.pix_to_face.is_cuda:
+        return False
+    if not torch.is_grad_enabled():
+        return True
+    tensors = [fragments.zbuf, fragments.bary_coords, fragments.dists, textures.maps_padded(), lights.ambient_color]
+    tensors += list(textures.verts_uvs_list())
+    return not any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def _per_view(z, N):
+    """znear / zfar as N Python floats (a camera's device tensor is read here, once per call)"""
+    if torch.is_tensor(z):
+        z = z.detach().reshape(-1).tolist()
+    else:
+        z = [float(z)]
+    if len(z) not in (1, N):
+        raise ValueError(f"expected 1 or {N} znear / zfar values, got {len(z)}")
+    return z * N if len(z) == 1 else z
+
+
+def _shade_hip(fragments, meshes, lights, blend_params, znear, zfar) -> torch.Tensor:
+    """(N,H,W,4): view n shades mesh n (or the only mesh) with sugar_amd.mesh_render.shade_textured"""
+    from sugar_amd.mesh_render import shade_textured
+    textures = meshes.textures
+    N = int(fragments.pix_to_face.shape[0])
+    maps, uvs, fuvs = textures.maps_padded(), textures.verts_uvs_list(), textures.faces_uvs_list()
+    if len(uvs) != N or maps.shape[0] != N:
+        raise ValueError(f"{N} views of fragments, but textures for {len(uvs)} meshes")
+    ambient = lights.ambient_color.detach().cpu().reshape(-1, 3)
+    bg = blend_params.background_color
+    bg = bg.detach().cpu() if torch.is_tensor(bg) else bg
+    bp = BlendParams(blend_params.sigma, blend_params.gamma, bg)
+    zn, zf = _per_view(znear, N), _per_view(zfar, N)
+    out, base = [], 0
+    for n in range(N):
+        frag = (fragments.pix_to_face[n], fragments.zbuf[n], fragments.bary_coords[n], fragments.dists[n])
+        out.append(shade_textured(frag, uvs[n].float(), fuvs[n].long(), maps[n].float(), sampling_mode="bilinear",
+                                  align_corners=textures.align_corners, padding_mode=textures.padding_mode, blend_params=bp,
+                                  znear=zn[n], zfar=zf[n], ambient=ambient[n if ambient.shape[0] > 1 else 0], face_index_base=base))
+        base += int(fuvs[n].shape[0])
+    return torch.stack(out)
+
+
 class SoftPhongShader(torch.nn.Module):
     def __init__(self, device="cpu", cameras=None, lights=None, materials=None, blend_params=None):
         super().__init__()
@@ -72,6 +119,9 @@ class SoftPhongShader(torch.nn.Module):
         if kwargs.get("materials", self.materials) is not None:
             raise NotImplementedError("the stand-in SoftPhongShader uses pytorch3d's default Materials only")
         blend_params = kwargs.get("blend_params", self.blend_params)
+        if _takes_hip_path(fragments, meshes.textures, lights):
+            return _shade_hip(fragments, meshes, lights, blend_params, kwargs.get("znear", getattr(cameras, "znear", 1.0)),
+                              kwargs.get("zfar", getattr(cameras, "zfar", 100.0)))
         texels = sample_textures_uv(meshes.textures, fragments)
         # phong_shading with AmbientLights and the default Materials (all colours 1): ambient = 1 * ambient_color, diffuse = specular = 0
         ambient = lights.ambient_color.to(texels.device)[:, None, None, None, :]

@@ -165,9 +165,10 @@ def project_verts(camera, verts: torch.Tensor) -> torch.Tensor:
     return torch.cat([ndc[..., :2], view[..., 2:3]], dim=-1)
 
 
-def rasterize_mesh(face_verts: torch.Tensor, image_size, znear: float, perspective_correct: bool = True) -> MeshFragments:
-    """hard z-buffer (K = 1) of one mesh's NDC face verts with the near-plane clip of a perspective camera (z = znear / 2), as the
-    stand-in MeshRasterizer runs it; the common case (nothing to clip) passes plain lists to the rasterizer"""
+def rasterize_mesh(face_verts: torch.Tensor, image_size, znear: float, perspective_correct: bool = True,
+                   faces_per_pixel: int = 1) -> MeshFragments:
+    """hard z-buffer (K = faces_per_pixel; the baking uses 1) of one mesh's NDC face verts with the near-plane clip of a perspective
+    camera (z = znear / 2), as the stand-in MeshRasterizer runs it; the common case (nothing to clip) passes plain lists to the rasterizer"""
     from .mesh_raster import rasterize_face_verts
     from .shims.pytorch3d.renderer.mesh.clip import ClipFrustum, clip_faces, convert_clipped_rasterization_to_original_faces
     F_ = int(face_verts.shape[0])
@@ -182,10 +183,11 @@ def rasterize_mesh(face_verts: torch.Tensor, image_size, znear: float, perspecti
         if clipped.faces_clipped_to_unclipped_idx is None:
             clipped = None
     if clipped is None:
-        p2f, zbuf, bary, dists = rasterize_face_verts(face_verts, [0], [F_], image_size, 0.0, 1, perspective_correct, False, False)
+        p2f, zbuf, bary, dists = rasterize_face_verts(face_verts, [0], [F_], image_size, 0.0, faces_per_pixel, perspective_correct, False,
+                                                      False)
     else:
-        p2f, zbuf, bary, dists = rasterize_face_verts(clipped.face_verts, [0], [int(clipped.face_verts.shape[0])], image_size, 0.0, 1,
-                                                      perspective_correct, False, False)
+        p2f, zbuf, bary, dists = rasterize_face_verts(clipped.face_verts, [0], [int(clipped.face_verts.shape[0])], image_size, 0.0,
+                                                      faces_per_pixel, perspective_correct, False, False)
         p2f, bary = convert_clipped_rasterization_to_original_faces(p2f, bary, clipped)
     return MeshFragments(p2f, zbuf, bary, dists)
 
