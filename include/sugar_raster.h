@@ -823,6 +823,29 @@ int sgr_mesh_clean_nonmanifold(int V, int F, const int64_t* sorted_keys, const i
                                const int32_t* faces, int32_t* face_remove, void* stream);
 int sgr_mesh_clean_referenced(int V, int F, const int32_t* faces, int32_t* vert_referenced, void* stream);
 
+/* ---- the sparse density-grid sweep: only the bricks a Gaussian can reach (csrc/sparse_sweep.hip; added under ABI version 4, additive) ---
+ * The grid meshgrid(X, Y, Z) (nx * ny * nz < 2^31, SGR_E_INVALID otherwise; the axes strictly ascending) is cut into bricks of 8 x 8 x 8
+ * points: brick (i, j, k) holds the points 8i .. 8i+7 and so on, edge bricks are partial, nb_a = ceil(n_a / 8), the linear brick index is
+ * (i nby + j) nbz + k.  The rule that flags a brick is stated at the top of csrc/sparse_sweep.hip and in DESIGN.md section 13.
+ * sgr_sparse_sweep_mark: flags[ceil16(nbx nby nbz)] (uint8, 16-byte aligned; zeroed here, padding included) = 1 for every brick the
+ *   index box of a reaching Gaussian touches.  packed: the [P][16] records of sgr_pack_gaussians; K: the neighbour count of the sweep;
+ *   level > 0, finite; gap[3] (float64, DEVICE): the largest spacing of each axis; big_list[P] (int32) and meta[4] (int32; zeroed here)
+ *   are scratch: meta[2] counts the Gaussians whose box exceeds 8 bricks, which a second launch spreads over workgroups.
+ * sgr_sparse_sweep_compact: has_box != 0 clears the flag of every brick all of whose in-grid points lie strictly inside lo < x, y, z < hi;
+ *   then list[0 .. meta[0]) (int32, capacity nbx nby nbz) = the flagged bricks in ascending order, meta[0] = their number and
+ *   meta[1] = 1 if an axis is not strictly ascending (the flags then mean nothing), else 0 -- all on the DEVICE: the caller's one read.
+ * sgr_sparse_sweep_points: out[(b - b0) 512 + l] = the grid point (lx, ly, lz) = (l >> 6, (l >> 3) & 7, l & 7) of brick list[b],
+ *   b in [b0, b1); a lane beyond the grid in an edge brick repeats the clamped in-grid point (always a valid, finite query).
+ * sgr_sparse_sweep_scatter: volume[point] = density[(b - b0) 512 + l] for the same lanes, in-grid lanes only.
+ * Plain byte stores for the flags, one integer atomic per large Gaussian, no float atomics; no call synchronises with the host. */
+int sgr_sparse_sweep_mark(int P, const float* packed, int K, float level, int nx, int ny, int nz, const float* X, const float* Y,
+                          const float* Z, const double* gap, uint8_t* flags, int32_t* big_list, int32_t* meta, void* stream);
+int sgr_sparse_sweep_compact(int nx, int ny, int nz, const float* X, const float* Y, const float* Z, int has_box, float lo, float hi,
+                             uint8_t* flags, int32_t* list, int32_t* meta, void* stream);
+int sgr_sparse_sweep_points(int nx, int ny, int nz, const float* X, const float* Y, const float* Z, const int32_t* list, int b0, int b1,
+                            float* out, void* stream);
+int sgr_sparse_sweep_scatter(int nx, int ny, int nz, const int32_t* list, int b0, int b1, const float* density, float* volume, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ SOURCES = {
     "mesh_bind.hip": ["-ffp-contract=off"],    # the binding restates the reference's individually rounded tensor arithmetic
     "marching_cubes.hip": ["-ffp-contract=off"],  # bit-identical with the serial restatement in tests/mc_restatement.py
     "mesh_decimate.hip": ["-ffp-contract=off"],   # bit-identical with the serial restatement in tests/decimate_restatement.py
+    "sparse_sweep.hip": ["-ffp-contract=off"],    # the brick flags follow the float64 restatement in tests/sparse_sweep_restatement.py
     "loss.hip": [],
     "adam.hip": [],
     "activations.hip": [],

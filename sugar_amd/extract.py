@@ -5,6 +5,9 @@ sugar_extractors/coarse_mesh.py (:623-757); its open3d calls (decimation, cleani
       on the grid meshgrid(X, Y, Z), swept in slabs: sgr_grid_points writes a slab's points, the HIP k-NN finds each point's K nearest
       Gaussians (what `get_gaussians_closest_to_samples` does), the HIP density field (`k_density_fwd`) sums their opacities, straight
       into the volume.  The reference's [512^3, 3] point tensor (1.6 GB) and its repeated `torch.cat` never exist.
+  density_grid_sparse(X, Y, Z, centers, inv_scaled_rot, strengths, level, ...)  -> the same volume wherever marching cubes at `level` reads
+      it, and 0 elsewhere: only the 8 x 8 x 8-point bricks a Gaussian can reach (csrc/sparse_sweep.hip) go through the k-NN and the
+      density kernel.  The mesh is bit-identical to the dense sweep's; `sweep="sparse"` below and `--sweep sparse` select it.
   extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, extent, ...) -> dict(verts, faces, normals, colors):
       the foreground grid over +-extent, the background grid over +-4 extent with the foreground box blanked (:698), marching cubes
       (sugar_amd.marching_cubes), colours 0.5 + C0 * dc of the nearest Gaussian (SH2RGB, :664), vertex normals, both meshes concatenated.
@@ -19,12 +22,13 @@ Deliberate differences from the reference:
     with its own stated rules (not open3d's implementation).  Normals and colours are computed after both.
 
     python -m sugar_amd.extract point_cloud.ply --out mesh.ply [--resolution 512 --level 0.3 --extent E --no-background]
-                                                               [--decimate N [--no-clean]]
+                                                               [--decimate N [--no-clean]] [--sweep {dense,sparse}]
 
 There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
 
 import argparse
+import math
 
 import torch
 
@@ -88,6 +92,94 @@ def density_grid(X, Y, Z, centers, inv_scaled_rot, strengths, K: int = 16, point
     return volume
 
 
+BRICK = 8  # points per brick edge of the sparse sweep (csrc/sparse_sweep.hip)
+
+
+def _sparse_sweep(X, Y, Z, centers, inv_scaled_rot, strengths, level, K, points_per_pass, zero_inside):
+    """-> (volume, flags uint8 [>= n_bricks], n_active, (nbx, nby, nbz)); the body of density_grid_sparse"""
+    level = float(level)
+    if not (math.isfinite(level) and level > 0):
+        raise ValueError("density_grid_sparse: level must be finite and positive (the skipped points hold 0, which must lie below it)")
+    for name, a in (("X", X), ("Y", Y), ("Z", Z)):
+        if torch.is_tensor(a) and a.dim() == 1 and not a.is_cuda and a.numel() > 1 and not bool((a[1:] > a[:-1]).all()):
+            raise ValueError(f"density_grid_sparse: {name} must be strictly ascending")   # (an axis on the device is checked there)
+    K, points_per_pass = int(K), int(points_per_pass)
+    if K < 1:
+        raise ValueError("density_grid_sparse: K must be positive")
+    if points_per_pass < 1:
+        raise ValueError("density_grid_sparse: points_per_pass must be positive")
+    if not torch.is_tensor(centers) or not centers.is_cuda:
+        raise RuntimeError("density_grid_sparse: centers must be a tensor on a ROCm device; there is no CPU fallback")
+    lib = _lib.load()
+    dev = centers.device
+    X, Y, Z = _axis(X, "X", dev), _axis(Y, "Y", dev), _axis(Z, "Z", dev)
+    nx, ny, nz = X.numel(), Y.numel(), Z.numel()
+    if nx * ny * nz >= _mc.MAX_POINTS:
+        raise ValueError(f"density_grid_sparse: a grid of {nx} x {ny} x {nz} points is refused: nx * ny * nz must stay below 2^31")
+    P = int(centers.shape[0])
+    if P < K:
+        raise ValueError(f"density_grid_sparse: {P} Gaussians are fewer than K = {K}")
+    ce = centers.detach().reshape(P, 3).contiguous().float()
+    Bm = inv_scaled_rot.detach().reshape(P, 9).contiguous().float()
+    st = strengths.detach().reshape(P).contiguous().float()
+    packed = _field._pack(lib, ce, Bm, st)
+    nb = tuple((n + BRICK - 1) // BRICK for n in (nx, ny, nz))
+    n_bricks = nb[0] * nb[1] * nb[2]
+    gap = torch.stack([(a[1:].double() - a[:-1].double()).max() if a.numel() > 1 else torch.zeros((), dtype=torch.float64, device=dev)
+                       for a in (X, Y, Z)])
+    flags = torch.empty((n_bricks + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+    big = torch.empty(P, dtype=torch.int32, device=dev)
+    meta = torch.empty(4, dtype=torch.int32, device=dev)
+    bricks = torch.empty(n_bricks, dtype=torch.int32, device=dev)
+    call("sgr_sparse_sweep_mark", dev, P, p(packed), K, level, nx, ny, nz, p(X), p(Y), p(Z), p(gap), p(flags), p(big), p(meta))
+    box = (float(zero_inside[0]), float(zero_inside[1])) if zero_inside is not None else (0.0, 0.0)
+    call("sgr_sparse_sweep_compact", dev, nx, ny, nz, p(X), p(Y), p(Z), int(zero_inside is not None), box[0], box[1], p(flags), p(bricks),
+         p(meta))
+    volume = torch.zeros(nx, ny, nz, dtype=torch.float32, device=dev)
+    n_active, bad_axis = meta.tolist()[:2]                                  # the one device -> host read: it sizes the chunk loop
+    if bad_axis:
+        raise ValueError("density_grid_sparse: X, Y and Z must be strictly ascending")
+    if n_active:
+        chunk = max(1, points_per_pass // (BRICK ** 3))
+        n_max = min(chunk, n_active) * BRICK ** 3
+        pts_buf = torch.empty(n_max, 3, dtype=torch.float32, device=dev)
+        opac = torch.empty(n_max, K, dtype=torch.float32, device=dev)
+        dens_buf = torch.empty(n_max, dtype=torch.float32, device=dev)
+        for b0 in range(0, n_active, chunk):
+            b1 = min(b0 + chunk, n_active)
+            n = (b1 - b0) * BRICK ** 3
+            pts, dens = pts_buf[:n], dens_buf[:n]
+            call("sgr_sparse_sweep_points", dev, nx, ny, nz, p(X), p(Y), p(Z), p(bricks), b0, b1, p(pts))
+            idx = knn_points(pts[None], ce[None], K=K).idx[0]
+            call("sgr_density_field_forward", dev, n, K, p(pts), p(idx), p(ce), p(Bm), p(st), 1.0, p(opac), p(dens), p(packed))
+            call("sgr_sparse_sweep_scatter", dev, nx, ny, nz, p(bricks), b0, b1, p(dens), p(volume))
+        if zero_inside is not None:
+            mx, my, mz = ((a > box[0]) & (a < box[1]) for a in (X, Y, Z))
+            volume.masked_fill_(mx[:, None, None] & my[None, :, None] & mz[None, None, :], 0.0)
+    return volume, flags, int(n_active), nb
+
+
+def density_grid_sparse(X, Y, Z, centers, inv_scaled_rot, strengths, level, K: int = 16, points_per_pass: int = 2_000_000, zero_inside=None,
+                        return_active: bool = False):
+    """volume[nx,ny,nz] float32 from which `marching_cubes(volume, level)` extracts, bit for bit, the mesh it extracts from
+    `density_grid(...)` with the same arguments -- at the cost of the k-NN for the grid points near the cloud only.  The grid is cut
+    into bricks of 8 x 8 x 8 points; a brick is ACTIVE when the box of a Gaussian that can lift a point to `level` touches it (the rule:
+    csrc/sparse_sweep.hip).  Every point of an active brick holds exactly the dense sweep's value; every other point
+    holds 0.0 where the dense sweep holds some value below `level` that no crossed edge reads.  Hence `level` must be finite and > 0,
+    and X, Y, Z strictly ascending (ValueError otherwise).  `zero_inside=(lo, hi)` additionally drops the bricks wholly inside the box
+    (the dense sweep writes 0 there); partly covered bricks are computed and blanked as in `density_grid`.  The result does not depend
+    on `points_per_pass` (chunks of max(1, points_per_pass // 512) bricks).  `return_active=True`: returns (volume, mask), mask bool
+    [ceil(nx/8), ceil(ny/8), ceil(nz/8)] of the active bricks.
+    Preconditions (outside them `density_grid` remains the tool): every inv_scaled_rot has orthogonal columns (it is R diag(1 / sigma));
+    all inputs are finite; P >= K.
+    One device -> host read per call: the number of active bricks, which sizes the chunk loop; with none active nothing further is
+    launched and the volume is all zero."""
+    volume, flags, _, nb = _sparse_sweep(X, Y, Z, centers, inv_scaled_rot, strengths, level, K, points_per_pass, zero_inside)
+    if return_active:
+        return volume, flags[:nb[0] * nb[1] * nb[2]].view(*nb).bool()
+    return volume
+
+
 def grid_to_world(verts_index, X, Y, Z):
     """index coordinates -> X[i] + t (X[i+1] - X[i]) per axis (i = floor, clamped so that the last grid point is i + 1 with t = 1)"""
     out = torch.empty_like(verts_index)
@@ -110,8 +202,12 @@ def nearest_gaussian_colors(verts, points, sh_dc):
     return 0.5 + SH_C0 * sh_dc.reshape(-1, 3)[idx], idx
 
 
-def _one_mesh(X, centers, B, strengths, sh_dc, level, K, points_per_pass, zero_inside, decimation_target=None, clean=False):
-    volume = density_grid(X, X, X, centers, B, strengths, K=K, points_per_pass=points_per_pass, zero_inside=zero_inside)
+def _one_mesh(X, centers, B, strengths, sh_dc, level, K, points_per_pass, zero_inside, decimation_target=None, clean=False, sweep="dense"):
+    total = ((X.numel() + BRICK - 1) // BRICK) ** 3
+    if sweep == "sparse":
+        volume, _, active, _ = _sparse_sweep(X, X, X, centers, B, strengths, level, K, points_per_pass, zero_inside)
+    else:
+        volume, active = density_grid(X, X, X, centers, B, strengths, K=K, points_per_pass=points_per_pass, zero_inside=zero_inside), total
     verts_index, faces = _mc.marching_cubes(volume, level)
     del volume
     verts = grid_to_world(verts_index, X, X, X)
@@ -121,19 +217,24 @@ def _one_mesh(X, centers, B, strengths, sh_dc, level, K, points_per_pass, zero_i
         verts, faces, _ = _decimate.clean(verts, faces)
     colors, _ = nearest_gaussian_colors(verts, centers, sh_dc)
     normals = _mc.vertex_normals(verts, faces) if verts.shape[0] else verts.new_zeros(0, 3)
-    return verts, faces, normals, colors
+    return verts, faces, normals, colors, (active, total)
 
 
 def extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, extent, resolution: int = 512, level: float = 0.3,
                                 background: bool = True, K: int = 16, points_per_pass: int = 2_000_000, decimation_target=None,
-                                clean: bool = False):
+                                clean: bool = False, sweep: str = "dense", return_stats: bool = False):
     """The marching-cubes mesh of a coarse SuGaR model.  points[P,3]; scales[P,3] (activated: `SuGaR.scaling`); quaternions[P,4] (real
     part first); opacities[P] or [P,1] in [0, 1] (`SuGaR.strengths`); sh_dc[P,3] or [P,1,3] (`_sh_coordinates_dc`); extent: the cameras'
     spatial extent (`get_cameras_spatial_extent()`); level: surface_levels[0].
     Returns dict(verts[V,3] float32, faces[F,3] int64, normals[V,3], colors[V,3] in RGB floats (0.5 + C0 dc, not clamped)), the foreground
     mesh first, then (background=True) the background mesh.  decimation_target=N: each of the two meshes is decimated to at most N faces
     (coarse_mesh.py:722-727); clean=True: each is then cleaned (:734-742).  With the defaults neither happens and the output is the full
-    marching-cubes mesh.  See the module docstring for the differences from the reference."""
+    marching-cubes mesh.  See the module docstring for the differences from the reference.
+    sweep="sparse": both volumes come from `density_grid_sparse` at `level` (which must then be finite and > 0): the same four tensors,
+    bit for bit, without the k-NN for the grid points no Gaussian reaches.  return_stats=True adds `active_bricks` and `total_bricks`,
+    one entry per pass (foreground, background); a dense pass sweeps every brick."""
+    if sweep not in ("dense", "sparse"):
+        raise ValueError(f"extract_mesh_marching_cubes: sweep must be 'dense' or 'sparse', not {sweep!r}")
     if not torch.is_tensor(points) or not points.is_cuda:
         raise RuntimeError("extract_mesh_marching_cubes: points must be a tensor on a ROCm device; there is no CPU fallback")
     dev = points.device
@@ -150,14 +251,17 @@ def extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, e
     lin = torch.linspace(-1, 1, resolution, device=dev)
     if decimation_target is not None and int(decimation_target) < 0:
         raise ValueError("extract_mesh_marching_cubes: decimation_target must not be negative")
-    post = (decimation_target, bool(clean))
+    post = (decimation_target, bool(clean), sweep)
     parts = [_one_mesh(lin * extent, centers, B, strengths, dc, level, K, points_per_pass, None, *post)]
     if background:
         parts.append(_one_mesh(lin * BACKGROUND_SCALE * extent, centers, B, strengths, dc, level, K, points_per_pass, (-extent, extent), *post))
     n_fg = parts[0][0].shape[0]
     verts = torch.cat([m[0] for m in parts])
     faces = torch.cat([m[1] + (n_fg if i else 0) for i, m in enumerate(parts)])
-    return dict(verts=verts, faces=faces, normals=torch.cat([m[2] for m in parts]), colors=torch.cat([m[3] for m in parts]))
+    mesh = dict(verts=verts, faces=faces, normals=torch.cat([m[2] for m in parts]), colors=torch.cat([m[3] for m in parts]))
+    if return_stats:
+        mesh.update(active_bricks=[m[4][0] for m in parts], total_bricks=[m[4][1] for m in parts])
+    return mesh
 
 
 def main(argv=None):
@@ -173,6 +277,8 @@ def main(argv=None):
     ap.add_argument("--decimate", type=int, default=None, metavar="N",
                     help="decimate the foreground and the background mesh to at most N faces each, then clean them")
     ap.add_argument("--no-clean", action="store_true", help="with --decimate: skip the cleaning passes")
+    ap.add_argument("--sweep", choices=("dense", "sparse"), default="dense",
+                    help="sparse: run the k-NN only in the 8^3-point bricks a Gaussian can reach; the mesh is the same, bit for bit")
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args(argv)
     g = io.load_gaussian_ply(a.point_cloud, device=a.device)
@@ -182,9 +288,14 @@ def main(argv=None):
         extent = float(r.kthvalue(max(1, int(0.99 * r.numel()))).values)
     mesh = extract_mesh_marching_cubes(g["xyz"], torch.exp(g["scaling"]), g["rotation"], torch.sigmoid(g["opacity"]), g["features"][:, 0, :],
                                        extent, resolution=a.resolution, level=a.level, background=not a.no_background,
-                                       decimation_target=a.decimate, clean=a.decimate is not None and not a.no_clean)
+                                       decimation_target=a.decimate, clean=a.decimate is not None and not a.no_clean, sweep=a.sweep,
+                                       return_stats=True)
     io.save_mesh_ply(a.out, mesh["verts"], mesh["faces"], normals=mesh["normals"], colors=mesh["colors"])
-    print(f"{a.out}: {mesh['verts'].shape[0]} vertices, {mesh['faces'].shape[0]} faces (extent {extent:.4g}, level {a.level})")
+    swept = ""
+    if a.sweep == "sparse":
+        act, tot = sum(mesh["active_bricks"]), sum(mesh["total_bricks"])
+        swept = f", sparse sweep: {act} of {tot} bricks active ({100.0 * act / tot:.2f} %)"
+    print(f"{a.out}: {mesh['verts'].shape[0]} vertices, {mesh['faces'].shape[0]} faces (extent {extent:.4g}, level {a.level}{swept})")
     return 0
 
 
