@@ -846,6 +846,27 @@ int sgr_sparse_sweep_points(int nx, int ny, int nz, const float* X, const float*
                             float* out, void* stream);
 int sgr_sparse_sweep_scatter(int nx, int ny, int nz, const int32_t* list, int b0, int b1, const float* density, float* volume, void* stream);
 
+/* ---- a local implicit surface from an oriented point cloud (csrc/point_surface.hip; added under ABI version 4, additive) -------------
+ * Implicit moving least squares over the K nearest cloud points of every query; NOT Poisson reconstruction (no global solve, no hole
+ * filling).  The rules -- the float32 order of operations, the defined / undefined test, the brick box rule and its slack, the
+ * spurious-vertex rule -- are stated at the top of csrc/point_surface.hip and in DESIGN.md section 16.  Grid and bricks as above.
+ * sgr_point_surface_mark: flags[ceil16(nbx nby nbz)] (uint8, 16-byte aligned; zeroed here, padding included) = 1 for every brick whose
+ *   in-grid point span, grown by radius (1 + 2^-20) on each axis, holds one of points[N,3]; meta[4] (int32) is zeroed here for
+ *   sgr_sparse_sweep_compact, which then lists the flagged bricks.  A non-finite point marks nothing.  radius > 0, finite.
+ * sgr_point_surface_pack: packed[N][8] (float, 16-byte aligned) = (px, py, pz, nx), (ny, nz, 0, 0).
+ * sgr_point_surface_eval: value[n] and (unless NULL) weight[n] of the queries[n,3] from their neighbour lists idx[n,K] (int64 rows into
+ *   the N packed records, in the k-NN's order; an entry outside [0, N) is skipped), 1 <= K <= 32.  value is NaN and weight 0 where no
+ *   listed point has s_k <= radius radius.  n = 0 is a no-op.
+ * sgr_point_surface_spurious: spurious[V] (uint8) = 1 iff volume[nx,ny,nz] at floor(c) or at ceil(c) is not finite, c = verts_index[v]
+ *   (the index coordinates marching cubes wrote, clamped to the grid).  V = 0 is a no-op.
+ * Plain stores only, no atomics; no call synchronises with the host. */
+int sgr_point_surface_mark(int N, const float* points, float radius, int nx, int ny, int nz, const float* X, const float* Y, const float* Z,
+                           uint8_t* flags, int32_t* meta, void* stream);
+int sgr_point_surface_pack(int N, const float* points, const float* normals, float* packed, void* stream);
+int sgr_point_surface_eval(long long n, int K, const float* queries, const int64_t* idx, int N, const float* packed, float radius,
+                           float* value, float* weight, void* stream);
+int sgr_point_surface_spurious(int V, const float* verts_index, int nx, int ny, int nz, const float* volume, uint8_t* spurious, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ SIGNATURES = {
     "sgr_sparse_sweep_compact": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp]),
     "sgr_sparse_sweep_points": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sgr_sparse_sweep_scatter": (_i, [_i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "sgr_point_surface_mark": (_i, [_i, _vp, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_point_surface_pack": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "sgr_point_surface_eval": (_i, [C.c_longlong, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp]),
+    "sgr_point_surface_spurious": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sgr_rasterize_meshes": (_i64, [_vp, _i64, _i64, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, ALLOC_FN, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -221,3 +221,46 @@ def clean(verts: torch.Tensor, faces: torch.Tensor, degenerate: bool = True, dup
     n_verts = int(vpos[-1])
     new_id = torch.where(ref > 0, vpos - 1, torch.full_like(vpos, -1))
     return v2[:n_verts], f2.to(torch.int64), new_id[vmap]
+
+
+def remove_vertices_by_mask(verts: torch.Tensor, faces: torch.Tensor, mask: torch.Tensor, *per_vertex, unreferenced: bool = False):
+    """open3d's `TriangleMesh.remove_vertices_by_mask` (coarse_mesh.py:395) with a stated rule: every vertex with mask[v] set is
+    removed, and with it every face that names one; `unreferenced=True` then also removes every vertex that no surviving face names.
+    The surviving vertices and faces keep their relative order (a stable compaction; faces are renumbered).  `per_vertex`: any number
+    of [V, ...] tensors, compacted like the vertices.  Returns (verts float32 [V',3], faces int64 [F',3], *per_vertex).
+    ONE device-to-host read: the pair (V', F'), which sizes the outputs.  A face naming a vertex outside [0, V) is removed."""
+    need_gpu("remove_vertices_by_mask", verts=verts, faces=faces, mask=mask)
+    _shapes("remove_vertices_by_mask", verts, faces)
+    V, F_ = int(verts.shape[0]), int(faces.shape[0])
+    if mask.dim() != 1 or int(mask.shape[0]) != V:
+        raise ValueError("remove_vertices_by_mask: mask must be [V]")
+    for a in per_vertex:
+        if not torch.is_tensor(a) or not a.is_cuda or a.dim() < 1 or int(a.shape[0]) != V:
+            raise ValueError("remove_vertices_by_mask: every per-vertex tensor must be a device tensor with V rows")
+    v = verts.detach().to(torch.float32).contiguous()
+    dev = v.device
+    gone = mask.detach().to(device=dev) != 0
+    if V == 0:
+        return (v, torch.zeros(0, 3, dtype=torch.int64, device=dev), *per_vertex)
+    if F_ == 0:
+        ids = torch.zeros(0, dtype=torch.int64, device=dev) if unreferenced else (~gone).nonzero(as_tuple=True)[0]   # (the one read)
+        return (v[ids], torch.zeros(0, 3, dtype=torch.int64, device=dev), *(a[ids] for a in per_vertex))
+    f = faces.detach().to(torch.int32).contiguous()
+    inside = ((f >= 0) & (f < V)).all(dim=1)
+    fkeep_b = inside & ~gone[f.clamp(0, V - 1).to(torch.int64)].any(dim=1)
+    fkeep = fkeep_b.to(torch.int32)
+    if unreferenced:
+        vkeep = torch.zeros(V, dtype=torch.int32, device=dev)
+        marked = torch.where(fkeep_b[:, None], f, torch.full_like(f, -1)).contiguous()    # (the kernel skips an index outside [0, V))
+        call("sgr_mesh_clean_referenced", dev, V, F_, ptr(marked), ptr(vkeep))
+        vkeep = vkeep * (~gone).to(torch.int32)
+    else:
+        vkeep = (~gone).to(torch.int32)
+    vpos, fpos = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
+    v2, f2 = torch.empty_like(v), torch.empty_like(f)
+    call("sgr_mesh_decimate_compact", dev, V, F_, ptr(vkeep), ptr(vpos), ptr(fkeep), ptr(fpos), None, None, ptr(v), ptr(f), None, None,
+         ptr(v2), ptr(f2))
+    src = torch.empty(V + 1, dtype=torch.int64, device=dev)       # src[j] = the input id of output vertex j (slot V: the removed ones)
+    src.scatter_(0, torch.where(vkeep > 0, vpos - 1, torch.full_like(vpos, V)), torch.arange(V, device=dev))
+    n_verts, n_faces = torch.stack([vpos[-1], fpos[-1]]).tolist()  # the one device-to-host read
+    return (v2[:n_verts], f2[:n_faces].to(torch.int64), *(a[src[:n_verts]] for a in per_vertex))

@@ -12,6 +12,11 @@ sugar_extractors/coarse_mesh.py (:623-757); its open3d calls (decimation, cleani
       the foreground grid over +-extent, the background grid over +-4 extent with the foreground box blanked (:698), marching cubes
       (sugar_amd.marching_cubes), colours 0.5 + C0 * dc of the nearest Gaussian (SH2RGB, :664), vertex normals, both meshes concatenated.
 
+  extract_mesh_level_sets(points, scales, quaternions, opacities, sh_dc, cameras, extent, ...) -> the same dict plus weights: the
+      reference's DEFAULT route (coarse_mesh.py:243-490) -- level-set points with normals sampled from every camera
+      (sugar_amd.sampler), split into foreground and background, outliers removed -- with sugar_amd.point_surface's local implicit
+      surface where the reference calls open3d's Poisson reconstruction.  It is not Poisson: holes stay open.  Opt-in (`--route levelset`).
+
 Deliberate differences from the reference:
   * vertices sit at the true grid coordinates X[i] + t (X[i+1] - X[i]).  The reference maps index coordinates with
     `-extent + vertices / resolution * 2 extent` (:661) although linspace(-1, 1, resolution) has a spacing of 2 / (resolution - 1): its
@@ -23,6 +28,9 @@ Deliberate differences from the reference:
 
     python -m sugar_amd.extract point_cloud.ply --out mesh.ply [--resolution 512 --level 0.3 --extent E --no-background]
                                                                [--decimate N [--no-clean]] [--sweep {dense,sparse}]
+    python -m sugar_amd.extract point_cloud.ply --route levelset --cameras cameras.json --out mesh.ply [--surface-level 0.3 --n-points N
+                                                               --radius-cells 3 --weight-quantile Q --resolution R --decimate N
+                                                               --no-clean --no-background]
 
 There is no CPU path: CPU tensors raise."""
 from __future__ import annotations
@@ -264,8 +272,101 @@ def extract_mesh_marching_cubes(points, scales, quaternions, opacities, sh_dc, e
     return mesh
 
 
-def main(argv=None):
-    from . import io
+def sample_level_set_cloud(points, scales, quaternions, opacities, cameras, surface_level: float = 0.3, n_total_points: int = 10_000_000,
+                           K: int = 16, seed: int = 0):
+    """(points[n,3], normals[n,3]) of the level set `surface_level`, sampled from every camera (coarse_mesh.py:243-327): per camera
+    `sampler.sample_level_sets(..., sync_free=True, seed=seed + i)` with n_total_points // len(cameras) + 1 pixels (:230); the rows go into
+    one preallocated buffer and ONE host wait at the end reads every camera's count."""
+    from . import sampler
+    dev = points.device
+    cameras = list(cameras)
+    if not cameras:
+        raise ValueError("sample_level_set_cloud: no cameras")
+    n = int(n_total_points) // len(cameras) + 1
+    means = points.detach().float().contiguous()
+    sc = scales.detach().float().contiguous()
+    q = torch.nn.functional.normalize(quaternions.detach().float(), dim=-1).contiguous()
+    op = opacities.detach().float().reshape(-1, 1).contiguous()
+    pts = torch.empty(len(cameras), n, 3, dtype=torch.float32, device=dev)
+    nrm = torch.empty(len(cameras), n, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(len(cameras), dtype=torch.int32, device=dev)
+    level = float(surface_level)
+    for i, cam in enumerate(cameras):
+        cam = cam._replace(viewmatrix=cam.viewmatrix.to(dev), projmatrix=cam.projmatrix.to(dev), campos=cam.campos.to(dev))
+        r = sampler.sample_level_sets(means, sc, q, op, cam, n_surface_points=n, surface_levels=(level,), K=int(K), sync_free=True,
+                                      seed=int(seed) + i)[level]
+        pts[i], nrm[i], counts[i] = r["intersection_points"], r["normals"], r["count"]
+    counts = counts.tolist()                                             # the one host wait of the sampling loop
+    return torch.cat([pts[i, :c] for i, c in enumerate(counts)]), torch.cat([nrm[i, :c] for i, c in enumerate(counts)])
+
+
+def extract_mesh_level_sets(points, scales, quaternions, opacities, sh_dc, cameras, extent, surface_level: float = 0.3,
+                            n_total_points: int = 10_000_000, resolution: int = 512, radius_cells: float = 3.0, K: int = 16,
+                            background: bool = True, outlier_std_ratio: float = 20.0, weight_quantile: float = 0.0, decimation_target=None,
+                            clean: bool = False, seed: int = 0, return_cloud: bool = False):
+    """The level-set mesh of a coarse SuGaR model: the reference's default route with a local implicit surface (sugar_amd.point_surface)
+    in the place of open3d's Poisson reconstruction.  Model arguments as `extract_mesh_marching_cubes`; cameras: `synthetic.Camera`-shaped
+    tuples (`io.cameras_from_json`).
+      sampling   `sample_level_set_cloud` at `surface_level` (one level per call; the caller loops over levels);
+      split      foreground: strictly inside +-extent on every axis; background: strictly inside +-4 extent and not foreground
+                 (coarse_mesh.py:353-359 with its default factors 1 and 4);
+      per part   `point_surface.statistical_outlier_mask(20, outlier_std_ratio)` (:382), then `point_surface.mesh_from_oriented_points` on
+                 linspace(-1, 1, resolution) x extent (x 4 extent for the background) with radius = radius_cells x the grid spacing,
+                 `weight_quantile`, `decimation_target` and `clean` passed through; a part with fewer than K points gives no mesh.
+    Returns dict(verts, faces, normals, colors, weights), the foreground first.  Differences from the reference, all deliberate: the
+    surface is NOT Poisson's -- it is defined only within `radius` of a sampled point, so unobserved regions stay open instead of being
+    closed by a smooth guess (the reference trims such regions by `vertices_density_quantile`); the vertex colours are 0.5 + C0 dc of the
+    nearest Gaussian, as on the marching-cubes route, not the rendered pixel colours of the sampled points.
+    return_cloud=True adds `cloud_points` and `cloud_normals` (after the split and the outlier mask, foreground first)."""
+    from . import point_surface as _ps
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise RuntimeError("extract_mesh_level_sets: points must be a tensor on a ROCm device; there is no CPU fallback")
+    dev = points.device
+    extent = float(extent)
+    if not extent > 0:
+        raise ValueError("extract_mesh_level_sets: extent must be positive")
+    resolution = int(resolution)
+    if resolution < 2 or resolution ** 3 >= _mc.MAX_POINTS:
+        raise ValueError("extract_mesh_level_sets: resolution must be in [2, 1290]")
+    if not float(radius_cells) > 0:
+        raise ValueError("extract_mesh_level_sets: radius_cells must be positive")
+    centers = points.detach().float().contiguous()
+    dc = sh_dc.detach().float().reshape(-1, 3)
+    cloud, cloud_n = sample_level_set_cloud(points, scales, quaternions, opacities, cameras, surface_level, n_total_points, K, seed)
+    reach = cloud.abs().max(dim=1).values if cloud.shape[0] else cloud.new_zeros(0)
+    fg = reach < extent
+    masks = [(fg, 1.0)] + ([((reach < BACKGROUND_SCALE * extent) & ~fg, BACKGROUND_SCALE)] if background else [])
+    lin = torch.linspace(-1, 1, resolution, device=dev)
+    parts, clouds = [], []
+    for mask, scale in masks:
+        pts, nrm = cloud[mask], cloud_n[mask]
+        if pts.shape[0]:
+            keep = _ps.statistical_outlier_mask(pts, 20, outlier_std_ratio)
+            pts, nrm = pts[keep], nrm[keep]
+        clouds.append((pts, nrm))
+        if pts.shape[0] < max(int(K), 1):
+            continue
+        X = lin * (scale * extent)
+        radius = float(torch.tensor(float(radius_cells) * 2.0 * scale * extent / (resolution - 1), dtype=torch.float32))
+        m = _ps.mesh_from_oriented_points(pts, nrm, X, X, X, radius=radius, K=K, weight_quantile=weight_quantile,
+                                          decimation_target=decimation_target, clean=clean)
+        m["colors"] = nearest_gaussian_colors(m["verts"], centers, dc)[0]
+        parts.append(m)
+    if not parts:
+        z = torch.zeros(0, 3, dtype=torch.float32, device=dev)
+        mesh = dict(verts=z, faces=torch.zeros(0, 3, dtype=torch.int64, device=dev), normals=z.clone(), colors=z.clone(), weights=z[:, 0].clone())
+    else:
+        offsets = [0]
+        for m in parts[:-1]:
+            offsets.append(offsets[-1] + m["verts"].shape[0])
+        mesh = {k: torch.cat([m[k] for m in parts]) for k in ("verts", "normals", "colors", "weights")}
+        mesh["faces"] = torch.cat([m["faces"] + o for m, o in zip(parts, offsets)])
+    if return_cloud:
+        mesh.update(cloud_points=torch.cat([c[0] for c in clouds]), cloud_normals=torch.cat([c[1] for c in clouds]))
+    return mesh
+
+
+def _parser():
     ap = argparse.ArgumentParser(description="marching-cubes mesh of a 3DGS / SuGaR point cloud (PLY) on the HIP kernels")
     ap.add_argument("point_cloud")
     ap.add_argument("--out", required=True)
@@ -280,12 +381,38 @@ def main(argv=None):
     ap.add_argument("--sweep", choices=("dense", "sparse"), default="dense",
                     help="sparse: run the k-NN only in the 8^3-point bricks a Gaussian can reach; the mesh is the same, bit for bit")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--route", choices=("marching-cubes", "levelset"), default="marching-cubes",
+                    help="levelset: sample level-set points with normals from every camera of --cameras and mesh them with a local "
+                         "implicit surface (not Poisson reconstruction: holes stay open)")
+    ap.add_argument("--cameras", default=None, help="levelset: the cameras.json of the training run")
+    ap.add_argument("--surface-level", type=float, default=0.3, help="levelset: the density level the points are sampled on")
+    ap.add_argument("--n-points", type=int, default=10_000_000, help="levelset: sampled pixels over all cameras")
+    ap.add_argument("--radius-cells", type=float, default=3.0, help="levelset: the support radius of the implicit, in grid spacings")
+    ap.add_argument("--weight-quantile", type=float, default=0.0, help="levelset: remove the vertices whose weight is below this quantile")
+    return ap
+
+
+def main(argv=None):
+    from . import io
+    ap = _parser()
     a = ap.parse_args(argv)
+    if a.route == "levelset" and not a.cameras:
+        ap.error("--route levelset requires --cameras")
     g = io.load_gaussian_ply(a.point_cloud, device=a.device)
     extent = a.extent
     if extent is None:
         r = g["xyz"].abs().max(dim=1).values
         extent = float(r.kthvalue(max(1, int(0.99 * r.numel()))).values)
+    if a.route == "levelset":
+        cams, _ = io.cameras_from_json(a.cameras, device=a.device)
+        mesh = extract_mesh_level_sets(g["xyz"], torch.exp(g["scaling"]), g["rotation"], torch.sigmoid(g["opacity"]), g["features"][:, 0, :],
+                                       cams, extent, surface_level=a.surface_level, n_total_points=a.n_points, resolution=a.resolution,
+                                       radius_cells=a.radius_cells, background=not a.no_background, weight_quantile=a.weight_quantile,
+                                       decimation_target=a.decimate, clean=a.decimate is not None and not a.no_clean)
+        io.save_mesh_ply(a.out, mesh["verts"], mesh["faces"], normals=mesh["normals"], colors=mesh["colors"])
+        print(f"{a.out}: {mesh['verts'].shape[0]} vertices, {mesh['faces'].shape[0]} faces (extent {extent:.4g}, level-set route at "
+              f"{a.surface_level}, local implicit surface, not Poisson)")
+        return 0
     mesh = extract_mesh_marching_cubes(g["xyz"], torch.exp(g["scaling"]), g["rotation"], torch.sigmoid(g["opacity"]), g["features"][:, 0, :],
                                        extent, resolution=a.resolution, level=a.level, background=not a.no_background,
                                        decimation_target=a.decimate, clean=a.decimate is not None and not a.no_clean, sweep=a.sweep,
