@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256) k_l1_ssim_bwd(int W, int H, int tiles_x, 
                                                      const float* __restrict__ Y,
                                                      Win win, const float* __restrict__ dm1, const float* __restrict__ ds1,
                                                      const float* __restrict__ ds12, const float* __restrict__ grad_loss,
-                                                     float lambda, float inv_n, float* __restrict__ dX,
+                                                     float lambda, float inv_n, double n, float* __restrict__ dX,
                                                      const float2* __restrict__ partial, int n_partial, float* __restrict__ loss)
 {
     __shared__ f2 sp[LR][LRP];
@@ -227,8 +227,10 @@ __global__ void __launch_bounds__(256) k_l1_ssim_bwd(int W, int H, int tiles_x, 
     __shared__ float hq[LR][LTP];
     int tile, c, tby, tbx;
     if (!xcd_tile(tiles_x, tiles_y, n_tiles, tile, c, tby, tbx, loss ? 8 : 0)) {
-        // (loss != NULL: the grid starts with eight workgroups more than tiles need; the first one reduces the forward's partials)
-        if (loss && blockIdx.x == 0) l1_ssim_finish<256>(partial, n_partial, 1.0 / (double)inv_n, lambda, loss);
+        // (loss != NULL: the grid starts with eight workgroups more than tiles need; the first one reduces the forward's partials.
+        // `n` is the pixel count itself, as k_l1_ssim_finish gets it: 1 / inv_n is off by the float32 rounding of inv_n, which moved
+        // the two means by an ulp against the stand-alone kernel's)
+        if (loss && blockIdx.x == 0) l1_ssim_finish<256>(partial, n_partial, n, lambda, loss);
         return;
     }
     const size_t plane = (size_t)c * W * H;
@@ -312,10 +314,14 @@ __global__ void __launch_bounds__(256) k_l1_ssim_bwd(int W, int H, int tiles_x, 
 Win make_window()
 {
     // gaussian(11, 1.5) of sugar_utils/loss_utils.py:23-25, float32 like torch.Tensor([...]) / sum
+    // The divisor is torch's float32 `gauss.sum()`, 3.7592328: the sum of the eleven float32 values rounded once.  (Adding them one
+    // after the other in float32 gives 3.7592325, one ulp less, and moves nine of the eleven taps by an ulp: the window then sums to
+    // 1 + 4e-8 instead of 1 - 3e-8 and every mean, S and gradient carries that factor up to four times.)
     Win w;
-    float s = 0.f;
-    for (int i = 0; i < 11; i++) { w.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += w.w[i]; }
-    for (int i = 0; i < 11; i++) w.w[i] = w.w[i] / s;
+    double s = 0.0;
+    for (int i = 0; i < 11; i++) { w.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += (double)w.w[i]; }
+    const float sf = (float)s;
+    for (int i = 0; i < 11; i++) w.w[i] = w.w[i] / sf;
     return w;
 }
 
@@ -373,11 +379,12 @@ int sgr_l1_ssim_backward_ex(int channels, int width, int height, const float* im
     const float* ds1 = reinterpret_cast<const float*>(scratch + plane);
     const float* ds12 = reinterpret_cast<const float*>(scratch + 2 * plane);
     const int tiles_x = (width + LT - 1) / LT, tiles_y = (height + LT - 1) / LT, n_tiles = tiles_x * tiles_y * channels;
-    const float inv_n = (float)(1.0 / ((double)channels * width * height));
+    const double n = (double)channels * width * height;
+    const float inv_n = (float)(1.0 / n);
     const float2* partial = reinterpret_cast<const float2*>(scratch + 3 * plane);  // (the forward's tiles are 32 x 28)
     const int n_partial = ((width + LT - 1) / LT) * ((height + LTY - 1) / LTY) * channels;
     hipLaunchKernelGGL(k_l1_ssim_bwd, dim3(8 * ((n_tiles + 7) / 8) + (loss_out ? 8 : 0)), dim3(256), 0, s, width, height, tiles_x, tiles_y,
-                       n_tiles, img, gt, make_window(), dm1, ds1, ds12, grad_loss, lambda, inv_n, grad_img, partial, n_partial, loss_out);
+                       n_tiles, img, gt, make_window(), dm1, ds1, ds12, grad_loss, lambda, inv_n, n, grad_img, partial, n_partial, loss_out);
     return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
 }
 
