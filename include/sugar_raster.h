@@ -386,7 +386,7 @@ int sgr_l1_ssim_backward_ex(int channels, int width, int height, const float* im
  * gaussian_splatting/scene/gaussian_model.py:152-166.  n floats in params / grads / exp_avg / exp_avg_sq (16-byte aligned);
  * the learning rate of element i is given by up to 8 segments k (HOST arrays): for seg_begin[k] <= i < seg_end[k] it is
  * seg_lr_a[k] when (i - seg_begin[k]) % seg_period[k] < seg_split[k], else seg_lr_b[k]; elements in no segment keep
- * lr 0 (their moments still update).  `step` is the 1-based step count used for bias correction; gradients are
+ * lr 0 (their moments still update); where segments overlap, the last listed one that holds the element decides.  `step` is the 1-based step count used for bias correction; gradients are
  * multiplied by `grad_scale` on the fly (1/world_size after a SUM all-reduce, so the mean needs no extra pass). */
 int sgr_adam_step(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,
                   const long long* seg_begin, const long long* seg_end, const float* seg_lr_a, const float* seg_lr_b,

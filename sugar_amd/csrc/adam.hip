@@ -45,10 +45,14 @@ __device__ __forceinline__ float lr_of1(const AdamSegs& sg, long long e)
 // 64-bit '%' made this kernel ALU-bound).
 __device__ __forceinline__ void lr_of4(const AdamSegs& sg, long long e0, long long wave_first, long long wave_last, float* lr)
 {
+    // (a later segment that holds only part of the wave's range overrides an earlier one there -- the last listed wins, seg_of -- so
+    // the wave is not uniform: per-element search)
     int ku = -1;
 #pragma clang loop unroll(disable)
-    for (int j = 0; j < sg.n; j++)
+    for (int j = 0; j < sg.n; j++) {
         if (wave_first >= sg.begin[j] && wave_last < sg.end[j]) ku = j;
+        else if (wave_last >= sg.begin[j] && wave_first < sg.end[j]) ku = -1;
+    }
     if (ku >= 0) {
         const float la = sg.lr_a[ku], lb = sg.lr_b[ku];
         if (la == lb) { lr[0] = lr[1] = lr[2] = lr[3] = la; return; }
@@ -67,6 +71,18 @@ __device__ __forceinline__ void lr_of4(const AdamSegs& sg, long long e0, long lo
 }
 
 typedef float f4 __attribute__((ext_vector_type(4)));
+
+// The update of one element, shared by both kernels' float4 loops and scalar tails.  The three multiply-adds are fused EXPLICITLY, the
+// way the compiler contracted the float4 loops: left to it, the scalar tails came out as packed multiplies and an unfused add, each
+// kernel's differently, and the last n % 4 elements of a tensor differed in the last bit between k_adam and k_adam_multi.
+__device__ __forceinline__ void adam_update(float g, float& p, float& m, float& v, float b1, float b2, float omb1, float omb2,
+                                            float eps, float step_size /* lr / (1 - b1^t) */, float bc2_sqrt)
+{
+    m = __builtin_fmaf(b1, m, omb1 * g);
+    v = __builtin_fmaf(b2, v, omb2 * g * g);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = __builtin_fmaf(-step_size, m / denom, p);
+}
 
 __global__ void __launch_bounds__(256) k_adam(long long n4, f4* __restrict__ p, const f4* __restrict__ g,
                                               f4* __restrict__ m, f4* __restrict__ v, AdamSegs sg, float b1, float b2, float omb1, float omb2,
@@ -99,12 +115,7 @@ __global__ void __launch_bounds__(256) k_adam(long long n4, f4* __restrict__ p, 
             lr_of4(sg, 4 * i, wf, wf + 255, lr);
         }
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            mf[c] = b1 * mf[c] + omb1 * gf[c];
-            vf[c] = b2 * vf[c] + omb2 * gf[c] * gf[c];
-            const float denom = sqrtf(vf[c]) / bc2_sqrt + eps;
-            pf[c] -= (lr[c] / bc1) * (mf[c] / denom);
-        }
+        for (int c = 0; c < 4; c++) adam_update(gf[c], pf[c], mf[c], vf[c], b1, b2, omb1, omb2, eps, lr[c] / bc1, bc2_sqrt);
         p[i] = pp;
         __builtin_nontemporal_store(mm, &m[i]);
         __builtin_nontemporal_store(vv, &v[i]);
@@ -117,10 +128,7 @@ __global__ void __launch_bounds__(256) k_adam(long long n4, f4* __restrict__ p, 
         if (e < extra_n) gg += extra[e];
         gg *= grad_scale;
         const float lr = lr_of1(sg, e);
-        const float mm = b1 * mf[e] + omb1 * gg, vv = b2 * vf[e] + omb2 * gg * gg;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        pf[e] -= (lr / bc1) * (mm / denom);
-        mf[e] = mm; vf[e] = vv;
+        adam_update(gg, pf[e], mf[e], vf[e], b1, b2, omb1, omb2, eps, lr / bc1, bc2_sqrt);
     }
 }
 
@@ -135,7 +143,7 @@ struct AdamMulti {
     unsigned int blk_begin[ADAM_MAX_TENSORS + 1];   // workgroups [blk_begin[t], blk_begin[t + 1]) stream tensor t
 };
 
-// the update of k_adam (same operations in the same order: bit-identical to one launch per tensor), the tensor chosen per workgroup
+// the update of k_adam (adam_update: bit-identical to one launch per tensor), the tensor chosen per workgroup
 __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti a)
 {
     int t = 0;
@@ -161,23 +169,14 @@ __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti a)
         float* vf = reinterpret_cast<float*>(&vv);
         const float* gf = reinterpret_cast<const float*>(&gg);
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            mf[c] = b1 * mf[c] + omb1 * gf[c];
-            vf[c] = b2 * vf[c] + omb2 * gf[c] * gf[c];
-            const float denom = sqrtf(vf[c]) / bc2_sqrt + eps;
-            pf[c] -= step_size * (mf[c] / denom);
-        }
+        for (int c = 0; c < 4; c++) adam_update(gf[c], pf[c], mf[c], vf[c], b1, b2, omb1, omb2, eps, step_size, bc2_sqrt);
         p[i] = pp;
         __builtin_nontemporal_store(mm, &m[i]);
         __builtin_nontemporal_store(vv, &v[i]);
     }
     if (lb == 0 && (long long)threadIdx.x < n - 4 * n4) {   // the last n % 4 elements
         const long long e = 4 * n4 + threadIdx.x;
-        const float gg = gg_[e];
-        const float mm = b1 * mm_[e] + omb1 * gg, vv = b2 * vv_[e] + omb2 * gg * gg;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        pp_[e] -= step_size * (mm / denom);
-        mm_[e] = mm; vv_[e] = vv;
+        adam_update(gg_[e], pp_[e], mm_[e], vv_[e], b1, b2, omb1, omb2, eps, step_size, bc2_sqrt);
     }
 }
 

@@ -27,25 +27,8 @@ def grad_sink(**buffers):
 
 def sh_grad_from_views_torch(means3D, campos_all, dcolor_all, sh_degree, out):
     """Torch restatement of sgr_sh_grad_from_views for the CPU rehearsal (per-view SH backward, backward.cu:47-97)."""
-    from oracle.torch_cpu_rasterizer import SH_C0, SH_C1, SH_C2, SH_C3
-    acc = torch.zeros_like(out)
-    for v in range(dcolor_all.shape[0]):
-        d = means3D - campos_all[v][None]
-        d = d / d.norm(dim=1, keepdim=True)
-        x, y, z = d[:, 0], d[:, 1], d[:, 2]
-        b = [torch.full_like(x, SH_C0)]
-        if sh_degree > 0:
-            b += [-SH_C1 * y, SH_C1 * z, -SH_C1 * x]
-        if sh_degree > 1:
-            xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
-            b += [SH_C2[0] * xy, SH_C2[1] * yz, SH_C2[2] * (2 * zz - xx - yy), SH_C2[3] * xz, SH_C2[4] * (xx - yy)]
-        if sh_degree > 2:
-            b += [SH_C3[0] * y * (3 * xx - yy), SH_C3[1] * xy * z, SH_C3[2] * y * (4 * zz - xx - yy),
-                  SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy), SH_C3[4] * x * (4 * zz - xx - yy), SH_C3[5] * z * (xx - yy),
-                  SH_C3[6] * x * (xx - 3 * yy)]
-        B = torch.stack(b, dim=1)  # [P, nb]
-        acc[:, : B.shape[1]] += B[:, :, None] * dcolor_all[v][:, None, :]
-    out.copy_(acc)
+    from oracle.optim_reference import sh_grad_from_views
+    out.copy_(sh_grad_from_views(means3D, campos_all, dcolor_all, sh_degree, out.shape[1], dtype=out.dtype)[0])
     return out
 
 
