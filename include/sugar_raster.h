@@ -867,6 +867,20 @@ int sgr_point_surface_eval(long long n, int K, const float* queries, const int64
                            float* value, float* weight, void* stream);
 int sgr_point_surface_spurious(int V, const float* verts_index, int nx, int ny, int nz, const float* volume, uint8_t* spurious, void* stream);
 
+/* ---- the border-face peel of the refined-mesh export (csrc/mesh_postprocess.hip; added under ABI version 4, additive) -----------------
+ * sugar_extractors/refined_mesh.py:133-147 as an integer rule.  Face (a, b, c) has the slots 3 f + k, k = 0, 1, 2, carrying the unordered
+ * pairs {a,b}, {b,c}, {c,a}; the live count of a pair is the number of slots of live faces that carry it (slots, not faces).  One
+ * iteration: a live face stays live iff all three of its pairs have live count >= 2, every count taken before any face of the iteration
+ * is removed.  `iterations` such steps are enqueued, with no early exit and no host synchronisation; an empty set stays empty.
+ * slot_edge[3F] (int32): the edge id in [0, E) of every slot (equal pairs, equal ids); edge_offsets[E+1] / edge_items[3F] (int32): the
+ *   edge -> slots CSR list.  An id or item outside its range counts as absent (the face dies), never an out-of-bounds access.
+ * live[F] (uint8, nonzero = live): read and overwritten in place with 0 / 1.  scratch: sgr_mesh_peel_border_scratch_bytes(E) bytes.
+ * F == 0 or iterations == 0 is a successful no-op (no pointer is read); F < 0, iterations < 0, 3 F >= 2^30, E outside 1 .. 3 F or a null
+ * pointer give SGR_E_INVALID.  Integer arithmetic and plain stores only: the result is the same bytes on every run. */
+size_t sgr_mesh_peel_border_scratch_bytes(int E);
+int sgr_mesh_peel_border(int F, int E, const int32_t* slot_edge, const int32_t* edge_offsets, const int32_t* edge_items, int iterations,
+                         uint8_t* live, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

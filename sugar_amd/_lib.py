@@ -135,6 +135,8 @@ SIGNATURES = {
     "sgr_point_surface_pack": (_i, [_i, _vp, _vp, _vp, _vp]),
     "sgr_point_surface_eval": (_i, [C.c_longlong, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp]),
     "sgr_point_surface_spurious": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sgr_mesh_peel_border_scratch_bytes": (_sz, [_i]),
+    "sgr_mesh_peel_border": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sgr_rasterize_meshes": (_i64, [_vp, _i64, _i64, _i, _i, _f, _i, _i, _i, _i, _vp, _sz, ALLOC_FN, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

@@ -34,6 +34,7 @@ SOURCES = {
     "mesh_decimate.hip": ["-ffp-contract=off"],   # bit-identical with the serial restatement in tests/decimate_restatement.py
     "sparse_sweep.hip": ["-ffp-contract=off"],    # the brick flags follow the float64 restatement in tests/sparse_sweep_restatement.py
     "point_surface.hip": ["-ffp-contract=off"],   # the implicit's values follow the float32 restatement in tests/point_surface_restatement.py
+    "mesh_postprocess.hip": [],                   # integer arithmetic only
     "loss.hip": [],
     "adam.hip": [],
     "activations.hip": [],

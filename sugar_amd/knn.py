@@ -3,7 +3,8 @@
   distCUDA2(points[P,3]) -> float[P]         simple-knn/spatial.cu:15-26 (mean squared distance to the 3 nearest others)
   knn_points(p1[1,N,3], p2[1,M,3], K)        the call shape SuGaR uses from pytorch3d.ops
                                              (sugar_scene/sugar_model.py:49,235,1028,1342): returns (dists[1,N,K] squared,
-                                             ascending; idx[1,N,K] int64; None)
+                                             ascending; idx[1,N,K] int64; None); also p1[1,N,2], p2[1,M,2], the call of
+                                             sugar_extractors/refined_mesh.py:143
 """
 from __future__ import annotations
 
@@ -49,14 +50,20 @@ def distCUDA2(points: torch.Tensor, method: str = "auto") -> torch.Tensor:
 
 def knn_points(p1: torch.Tensor, p2: torch.Tensor, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, version: int = -1,
                return_nn: bool = False, return_sorted: bool = True, method: str = "auto") -> _KNN:
-    """pytorch3d.ops.knn_points for the call shape SuGaR uses (one cloud per call, 3-D, squared L2, sorted).  The
-    remaining pytorch3d arguments are accepted for signature compatibility; unsupported values raise."""
+    """pytorch3d.ops.knn_points for the call shapes SuGaR uses (one cloud per call, squared L2, sorted): 3-D points, and the 2-D
+    points of the refined-mesh extractor's border test (refined_mesh.py:143), which take the 3-D kernels with a zero third
+    coordinate -- the same floats, (dx dx + dy dy) + 0 0 -- and get 2-D rows back from `return_nn`.  The remaining pytorch3d
+    arguments are accepted for signature compatibility; unsupported values raise."""
     if lengths1 is not None or lengths2 is not None or norm != 2:
         raise NotImplementedError("knn_points: lengths1/lengths2/norm=1 are not supported by the HIP k-NN")
     lib = _lib.load()
-    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != 1 or p2.shape[0] != 1 or p1.shape[2] != 3 or p2.shape[2] != 3:
-        raise RuntimeError("knn_points: expected p1[1,N,3], p2[1,M,3] (the shapes SuGaR uses)")
+    if (p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != 1 or p2.shape[0] != 1 or p1.shape[2] not in (2, 3)
+            or p2.shape[2] != p1.shape[2]):
+        raise RuntimeError("knn_points: expected p1[1,N,3], p2[1,M,3] (the shapes SuGaR uses) or p1[1,N,2], p2[1,M,2]")
     q, r = _check(p1[0], "p1"), _check(p2[0], "p2")
+    r_out = r
+    if q.shape[1] == 2:
+        q, r = torch.nn.functional.pad(q, (0, 1)), torch.nn.functional.pad(r, (0, 1))
     N, M = q.shape[0], r.shape[0]
     K_req = int(K)
     if K_req < 1 or K_req > SUPPORTED_K[-1]:
@@ -71,7 +78,7 @@ def knn_points(p1: torch.Tensor, p2: torch.Tensor, lengths1=None, lengths2=None,
         call("sgr_knn", q.device, N, ptr(q), M, ptr(r), int(K), ptr(d), ptr(i))
     if K != K_req:
         d, i = d[:, :K_req].contiguous(), i[:, :K_req].contiguous()
-    return _KNN(d[None], i[None], r[i][None] if return_nn else None)
+    return _KNN(d[None], i[None], r_out[i][None] if return_nn else None)
 
 
 def knn_points_pytorch3d(original):
