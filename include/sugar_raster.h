@@ -565,6 +565,56 @@ int sgr_density_field_backward_gather(int N, int K, int P, const float* x, const
 size_t sgr_scatter_add_rows_scratch_bytes(long long N, int P);
 int sgr_scatter_add_rows(long long N, const int64_t* idx, const float* src, int W, int P, float* out, char* scratch, void* stream);
 
+/* ---- the coarse stage's SDF regulariser (csrc/sdf_regulariser.hip; added under ABI version 4, additive) -----------------------------
+ * The tensor code of four SuGaR methods (sugar_scene/sugar_model.py) as one forward and one backward each.  All tensors float32 and
+ * contiguous unless said otherwise, indices int64 (negative ones wrap once; a row outside [-P, P) contributes nothing and is never
+ * dereferenced), quaternions real part first and 16-byte aligned.  Every per-Gaussian gradient ([P, .]) is WRITTEN completely -- rows
+ * that nothing references are zero -- and summed in a fixed order over the stably grouped entries, sixteen lanes per Gaussian, without
+ * float atomics: bit-identical from run to run.  No host synchronisation.  N, M < 2^32; N * K < 2^32.
+ *
+ * sgr_sample_transform_*  (sample_points_in_gaussians, :924-926): out[n] = points[i] + rot(q_i, factor * scaling[i] (.) noise[n]),
+ *   i = idx[n], rot(q, v) = vector part of q (x) (0, v) (x) conj(q) with q as given (not normalised).  The backward writes
+ *   dL_dpoints[P,3], dL_dquaternions[P,4], dL_dscaling[P,3]; scratch: sgr_sample_transform_backward_scratch_bytes(N, P).
+ * sgr_smallest_axis_*  (get_smallest_axis, :930-944): axis[p] = column j of R(q_p), j = argmin scaling[p] (the lowest j on ties),
+ *   R = I + 2 / |q|^2 * M(q); axis_idx[P] (int64, may be NULL) = j.  The backward writes dL_dquaternions[P,4].
+ * sgr_depth_lookup_*  (get_points_depth_in_depth_map, :1318-1333): c = [x y z 1] * projection (projection[16], row-major, row
+ *   vectors, on the device), ndc = c.xy / c.w, g = -min(H, W) / (W, H) * ndc, then grid_sample(bilinear, padding 'border',
+ *   align_corners False) of the depth map, which is read as depth[y * stride_y + x * stride_x] (strides in elements).  The backward
+ *   writes dL_dpoints_cam[M,3] (may be NULL) and ADDS the taps into dL_ddepth[H * W] (contiguous, zeroed by the call; may be NULL) with
+ *   float atomics: that one output is not bit-reproducible.
+ * sgr_sdf_field_*  (get_field_values with beta_mode 'average', :1247-1307): neighbour opacities and density as
+ *   sgr_density_field_forward, then d' = density < 1 ? density : density / (density + 1e-12),
+ *   beta = mean_k min_scaling[nbr_k], sdf = beta * (sqrt(-2 ln max(d', opacity_min_clamp)) - sqrt(-2 ln min(density_threshold, 1))).
+ *   neighbor_opacities may be NULL; packed as for sgr_density_field_forward (sgr_pack_gaussians, may be NULL).  The backward takes the
+ *   forward's density and beta, any of the four output gradients (NULL = zero) and writes dL_dx[N,3] (may be NULL), the 13 per-Gaussian
+ *   sums of sgr_density_field_backward_gather and dL_dmin_scaling[P]; the tail's derivative follows the reference's operation order,
+ *   so a row with density >= 1 and a gradient on sdf carries sqrt(0)'s non-finite derivative, as float32 autograd gives it there.
+ *   scratch: sgr_sdf_field_backward_scratch_bytes(N, K, P). */
+int sgr_sample_transform_forward(long long N, int P, const int64_t* idx, const float* points, const float* quaternions,
+                                 const float* scaling, const float* noise, float factor, float* out, void* stream);
+size_t sgr_sample_transform_backward_scratch_bytes(long long N, int P);
+int sgr_sample_transform_backward(long long N, int P, const int64_t* idx, const float* quaternions, const float* scaling,
+                                  const float* noise, float factor, const float* dL_dout, float* dL_dpoints, float* dL_dquaternions,
+                                  float* dL_dscaling, char* scratch, void* stream);
+int sgr_smallest_axis_forward(int P, const float* quaternions, const float* scaling, float* axis, int64_t* axis_idx, void* stream);
+int sgr_smallest_axis_backward(int P, const float* quaternions, const float* scaling, const float* dL_daxis, float* dL_dquaternions,
+                               void* stream);
+int sgr_depth_lookup_forward(long long M, const float* points_cam, const float* projection, const float* depth, long long stride_y,
+                             long long stride_x, int height, int width, float* out, void* stream);
+int sgr_depth_lookup_backward(long long M, const float* points_cam, const float* projection, const float* depth, long long stride_y,
+                              long long stride_x, int height, int width, const float* dL_dout, float* dL_dpoints_cam, float* dL_ddepth,
+                              void* stream);
+int sgr_sdf_field_forward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
+                          const float* strengths, const float* min_scaling, float density_factor, float density_threshold,
+                          float opacity_min_clamp, float* neighbor_opacities, float* density, float* beta, float* sdf,
+                          const float* packed, void* stream);
+size_t sgr_sdf_field_backward_scratch_bytes(int N, int K, int P);
+int sgr_sdf_field_backward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
+                           const float* strengths, float density_factor, float density_threshold, float opacity_min_clamp,
+                           const float* density, const float* beta, const float* dL_dopacities, const float* dL_ddensity,
+                           const float* dL_dbeta, const float* dL_dsdf, float* dL_dx, float* dL_dcenters, float* dL_dinv_scaled_rot,
+                           float* dL_dstrengths, float* dL_dmin_scaling, char* scratch, const float* packed, void* stream);
+
 int sgr_level_set_points(int N, int K, const float* world_points, const int64_t* nbr_idx, const float* cam_center,
                          const float* centers, const float* inv_scaled_rot, const float* strengths,
                          const float* gaussian_std, int n_levels, const float* levels_host, int n_range, float range_size,

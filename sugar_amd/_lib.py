@@ -78,6 +78,17 @@ SIGNATURES = {
     "sgr_scatter_add_rows_scratch_bytes": (_sz, [C.c_longlong, _i]),
     "sgr_scatter_add_rows": (_i, [C.c_longlong, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "sgr_density_field_backward_gather": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_sample_transform_forward": (_i, [C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "sgr_sample_transform_backward_scratch_bytes": (_sz, [C.c_longlong, _i]),
+    "sgr_sample_transform_backward": (_i, [C.c_longlong, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_smallest_axis_forward": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_smallest_axis_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_depth_lookup_forward": (_i, [C.c_longlong, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _vp, _vp]),
+    "sgr_depth_lookup_backward": (_i, [C.c_longlong, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _i, _i, _vp, _vp, _vp, _vp]),
+    "sgr_sdf_field_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sgr_sdf_field_backward_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sgr_sdf_field_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
     "sgr_scaled_rotation_forward": (_i, [_i, _vp, _vp, _i, _vp, _vp]),
     "sgr_scaled_rotation_backward": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sgr_pack_gaussians": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),

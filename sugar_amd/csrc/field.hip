@@ -14,6 +14,7 @@
 //                   sample costs 3 FMAs + |.|^2 + one exp per neighbour instead of a 3x3 product.
 #include "../../include/sugar_raster.h"
 #include "sgr_device.h"
+#include "sgr_group.h"
 
 namespace {
 
@@ -775,6 +776,13 @@ __global__ void __launch_bounds__(128) k_level_set(int N, int K, const float* __
 }
 
 }  // namespace
+
+// the stable grouping above with external linkage, for csrc/sdf_regulariser.hip (declared in sgr_group.h)
+size_t sgr_group_scratch_bytes(size_t M) { return carve_group(nullptr, M).total; }
+int sgr_group_by_key(long long M, const long long* keys64, int P, char* scratch, uint32_t* start, const uint32_t** list_out, hipStream_t s)
+{
+    return launch_group_by_key(M, keys64, P, scratch, start, list_out, s);
+}
 
 extern "C" {
 

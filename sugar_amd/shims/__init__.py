@@ -23,7 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_gathers=False, patch_densifier=False,
-            patch_texture=False, patch_binding=False) -> str:
+            patch_texture=False, patch_binding=False, patch_regulariser=False) -> str:
     """Returns "patched" (real pytorch3d found, knn_points redirected) or "shim" (stand-in package activated).
 
     `patch_sugar`: also route SuGaR's own Gaussian-buffer-sharing tensor code -- `get_points_rgb`, `get_covariance(return_sqrt)`,
@@ -41,7 +41,10 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
     sugar_amd.texture (install_texture); pass the module like `patch_sugar`, or True.
     `patch_binding`: the refine stage's mesh binding -- `SuGaR.points / scaling / quaternions` of a model bound to a surface mesh -- and
     the stand-in `pytorch3d.loss.mesh_normal_consistency` of a single mesh run on the HIP kernels of sugar_amd.mesh_bind
-    (install_binding); pass the module like `patch_sugar`, or True."""
+    (install_binding); pass the module like `patch_sugar`, or True.
+    `patch_regulariser`: the coarse stage's SDF regulariser -- `SuGaR.sample_points_in_gaussians`, `get_smallest_axis`,
+    `get_points_depth_in_depth_map` and the whole of `get_field_values` (beta_mode 'average') -- on the HIP kernels of
+    sugar_amd.sdf_regulariser (sugar_amd.sugar_patch.install_regulariser); pass the module like `patch_sugar`, or True."""
     real_plyfile = _real_package("plyfile")  # (probed BEFORE the stand-in directory can shadow it on sys.path)
     real_mcubes = _real_package("mcubes")
     mode = _install_pytorch3d()
@@ -65,6 +68,10 @@ def install(patch_sugar=False, patch_losses=False, patch_optimizer=False, patch_
         install_texture(importlib.import_module("sugar_scene.sugar_model") if patch_texture is True else patch_texture)
     if patch_binding:
         install_binding(importlib.import_module("sugar_scene.sugar_model") if patch_binding is True else patch_binding)
+    if patch_regulariser:
+        from .. import sugar_patch
+        module = importlib.import_module("sugar_scene.sugar_model") if patch_regulariser is True else patch_regulariser
+        sugar_patch.install_regulariser(module)
     return mode
 
 

@@ -11,6 +11,15 @@ with functions of the same signature and return values.  Each replacement takes 
 ROCm device and the argument combinations listed below -- and hands every other call to the reference's own method, which
 stays reachable as `SuGaR._sugar_amd_original[name]`.  `uninstall(sm)` puts the originals back.
 
+`install_regulariser(sm)` (opt-in, separate from the above) binds the four methods the coarse trainer's SDF regulariser calls
+
+    SuGaR.sample_points_in_gaussians                       sugar_model.py:885-928    -> sgr_sample_transform_*  (sdf_regulariser.py)
+    SuGaR.get_smallest_axis  (and so get_normals())        sugar_model.py:930-968    -> sgr_smallest_axis_*
+    SuGaR.get_points_depth_in_depth_map                    sugar_model.py:1318-1333  -> sgr_depth_lookup_*
+    SuGaR.get_field_values  (beta_mode 'average', no sdf_grad)   :1247-1316          -> sgr_sdf_field_*
+
+on top of whatever is bound, the same way; `uninstall_regulariser(sm)` takes them off again.
+
 The replacements are written against the attributes SuGaR exposes (`points`, `scaling`, `quaternions`, `strengths`,
 `sh_coordinates`, `knn_idx`, `knn_to_track`, `image_height`, `image_width`, `get_beta`, `render_image_gaussian_rasterizer`,
 `get_gaussians_closest_to_samples`), so the GPU tests can drive them with a small stand-in object holding a fixture of the
@@ -58,7 +67,8 @@ def get_field_values(self, x, gaussian_idx=None, closest_gaussians_idx=None, gau
     """sugar_model.py:1247-1316.  The neighbour gather, the warp, the exponentials and their sum (and, in the backward, the
     scatter of their gradients) are the fused kernels; everything after the densities is the reference's own arithmetic on
     [N] / [N,K] tensors.  `return_sdf_grad=True` needs the per-neighbour warped shifts and goes to the reference's code."""
-    if _orig is not None and (return_sdf_grad or not x.is_cuda):
+    if _orig is not None and (return_sdf_grad or not x.is_cuda or (getattr(_orig, "_sugar_amd_regulariser", False) and _field_tail_covered(
+            self, x, return_sdf, return_beta, return_sdf_grad, density_threshold, opacity_min_clamp))):   # (install_regulariser ran first)
         return _orig(self, x, gaussian_idx=gaussian_idx, closest_gaussians_idx=closest_gaussians_idx,
                      gaussian_strengths=gaussian_strengths, gaussian_centers=gaussian_centers,
                      gaussian_inv_scaled_rotation=gaussian_inv_scaled_rotation, return_sdf=return_sdf,
@@ -427,7 +437,177 @@ def uninstall_binding(sugar_model_module):
             setattr(cls, name, _row_gather_property(orig))
 
 
+# ------------------------------------------------------------------------- the coarse stage's SDF regulariser (opt-in)
+# Four methods the unmodified coarse trainer calls (sugar_trainers/coarse_sdf.py:566-716), on the kernels of csrc/sdf_regulariser.hip
+# (sugar_amd.sdf_regulariser).  Each takes over float32 tensors on a ROCm device and the argument combinations listed with it; every
+# other call goes to `_prev`: whatever was bound when `install_regulariser` ran -- the reference's method, or `install`'s binding.
+REGULARISER_PATCHED = ("sample_points_in_gaussians", "get_smallest_axis", "get_points_depth_in_depth_map", "get_field_values")
+
+
+def _gpu_f32(*ts):
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def sample_points_in_gaussians(self, num_samples, sampling_scale_factor=1., mask=None, probabilities_proportional_to_opacity=False,
+                               probabilities_proportional_to_volume=True, _prev=None):
+    """sugar_model.py:885-928.  The draws are the reference's, statement by statement -- the mask handling, `torch.multinomial`, the
+    index composition through the boolean mask (with its host synchronisation), then `torch.randn_like` -- so a seeded run samples what
+    the reference's method samples on the same device; the arithmetic after them (:924-926: three row gathers, `quaternion_apply`, ~20
+    launches and their autograd twins) is one kernel each way."""
+    points, quaternions, all_scaling = self.points, self.quaternions, self.scaling
+    if _prev is not None and not (_gpu_f32(points, quaternions, all_scaling) and _number(sampling_scale_factor)):
+        return _prev(self, num_samples, sampling_scale_factor=sampling_scale_factor, mask=mask,
+                     probabilities_proportional_to_opacity=probabilities_proportional_to_opacity,
+                     probabilities_proportional_to_volume=probabilities_proportional_to_volume)
+    from .sdf_regulariser import _plain, sample_transform
+    with torch.no_grad():   # (the probabilities carry no gradient: `multinomial` is where the reference's graph ends too)
+        scaling = _plain(all_scaling) if mask is None else _plain(all_scaling)[mask]
+        if probabilities_proportional_to_volume:
+            areas = scaling[..., 0] * scaling[..., 1] * scaling[..., 2]
+        else:
+            areas = torch.ones_like(scaling[..., 0])
+        if probabilities_proportional_to_opacity:
+            if mask is None:
+                areas = areas * self.strengths.view(-1)
+            else:
+                areas = areas * self.strengths[mask].view(-1)
+        areas = areas.abs()
+        cum_probs = areas / areas.sum(dim=-1, keepdim=True)
+        random_indices = torch.multinomial(cum_probs, num_samples=num_samples, replacement=True)
+        if mask is not None:
+            valid_indices = torch.arange(self.n_points, device=self.device)[mask]
+            random_indices = valid_indices[random_indices]
+        noise = torch.randn_like(points.new_empty(random_indices.shape + (3,)))   # the draw of `randn_like(self.points[random_indices])`
+    return sample_transform(points, quaternions, all_scaling, random_indices, noise, float(sampling_scale_factor)), random_indices
+
+
+def get_smallest_axis(self, return_idx=False, _prev=None):
+    """sugar_model.py:930-944, and through it `get_normals(estimate_from_points=False)` of a model that is not bound to a mesh
+    (:967): `quaternion_to_matrix` over all P, `expand` and `gather` are one kernel each way.  A mesh-bound model goes to `_prev`."""
+    quaternions, scaling = self.quaternions, self.scaling
+    if _prev is not None and (not _gpu_f32(quaternions, scaling) or getattr(self, "binded_to_surface_mesh", False)):
+        return _prev(self, return_idx=return_idx)
+    from .sdf_regulariser import smallest_axis
+    axis, axis_idx = smallest_axis(quaternions, scaling)
+    return (axis, axis_idx) if return_idx else axis
+
+
+def get_points_depth_in_depth_map(self, fov_camera, depth, points_in_camera_space, _prev=None):
+    """sugar_model.py:1318-1333: `transform_points`, the in-place scaling and `grid_sample` (with its backward) are one kernel each
+    way; the depth map -- `image[..., 0]` of an [H,W,3] render -- is read through its strides.  One camera, a [H,W] map of the
+    model's image size and [M,3] points; anything else goes to `_prev`."""
+    ok = (_gpu_f32(depth, points_in_camera_space) and depth.dim() == 2 and points_in_camera_space.dim() == 2
+          and points_in_camera_space.shape[-1] == 3 and tuple(depth.shape) == (self.image_height, self.image_width))
+    projection = fov_camera.get_projection_transform().get_matrix() if ok else None
+    ok = ok and _gpu_f32(projection) and projection.numel() == 16
+    if _prev is not None and not ok:
+        return _prev(self, fov_camera, depth, points_in_camera_space)
+    from .sdf_regulariser import depth_lookup
+    return depth_lookup(projection, depth, points_in_camera_space)
+
+
+def _field_tail_covered(self, x, return_sdf, return_beta, return_sdf_grad, density_threshold, opacity_min_clamp):
+    """the calls `get_field_values_with_sdf_tail` implements"""
+    return (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and not return_sdf_grad and bool(return_sdf or return_beta)
+            and getattr(self, "beta_mode", None) == "average" and _number(density_threshold) and density_threshold > 0
+            and _number(opacity_min_clamp))
+
+
+def get_field_values_with_sdf_tail(self, x, gaussian_idx=None, closest_gaussians_idx=None, gaussian_strengths=None,
+                                   gaussian_centers=None, gaussian_inv_scaled_rotation=None, return_sdf=True, density_threshold=1.,
+                                   density_factor=1., return_sdf_grad=False, sdf_grad_max_value=10., opacity_min_clamp=1e-16,
+                                   return_closest_gaussian_opacities=False, return_beta=False, _prev=None):
+    """sugar_model.py:1247-1316 as ONE forward and ONE backward when `beta_mode == 'average'`, `return_sdf_grad=False` and the sdf or
+    beta is asked for: the density field, `get_beta('average')` (:1195 -- a [N,16] gather of a plain tensor whose stock backward is an
+    `index_put_(accumulate=True)` over 16 N indices) and the sdf (:1296-1306).  `scaling.min(-1)[0]` stays a torch op over [P]; autograd
+    carries its gradient on to `_scales`.  The other beta modes, `return_sdf_grad=True` and density-only calls go to `_prev`."""
+    if _prev is not None and not _field_tail_covered(self, x, return_sdf, return_beta, return_sdf_grad, density_threshold, opacity_min_clamp):
+        return _prev(self, x, gaussian_idx=gaussian_idx, closest_gaussians_idx=closest_gaussians_idx,
+                     gaussian_strengths=gaussian_strengths, gaussian_centers=gaussian_centers,
+                     gaussian_inv_scaled_rotation=gaussian_inv_scaled_rotation, return_sdf=return_sdf,
+                     density_threshold=density_threshold, density_factor=density_factor, return_sdf_grad=return_sdf_grad,
+                     sdf_grad_max_value=sdf_grad_max_value, opacity_min_clamp=opacity_min_clamp,
+                     return_closest_gaussian_opacities=return_closest_gaussian_opacities, return_beta=return_beta)
+    from .sdf_regulariser import _plain, sdf_field
+    if gaussian_strengths is None:
+        gaussian_strengths = self.strengths
+    if gaussian_centers is None:
+        gaussian_centers = self.points
+    if gaussian_inv_scaled_rotation is None:
+        gaussian_inv_scaled_rotation = self.get_covariance(return_full_matrix=True, return_sqrt=True, inverse_scales=True)
+    if closest_gaussians_idx is None:
+        closest_gaussians_idx = self.knn_idx[gaussian_idx]
+    min_scaling = _plain(self.scaling).min(dim=-1)[0]                                                        # :1195
+    neighbor_opacities, density, beta, sdf = sdf_field(x, closest_gaussians_idx, gaussian_centers, gaussian_inv_scaled_rotation,
+                                                       gaussian_strengths, min_scaling, density_factor, density_threshold,
+                                                       opacity_min_clamp)
+    fields = {'density': density}
+    if return_closest_gaussian_opacities:
+        fields['closest_gaussian_opacities'] = neighbor_opacities
+    if return_beta:
+        fields['beta'] = beta
+    if return_sdf:
+        fields['sdf'] = sdf
+    return fields
+
+
+_REGULARISER_IMPL = dict(sample_points_in_gaussians=sample_points_in_gaussians, get_smallest_axis=get_smallest_axis,
+                         get_points_depth_in_depth_map=get_points_depth_in_depth_map, get_field_values=get_field_values_with_sdf_tail)
+_REGULARISER_KEY = "_sugar_amd_regulariser_original"
+
+
+def _regulariser_binding(impl, prev, reference_method):
+    @functools.wraps(reference_method)          # the reference's name, doc and signature (inspect follows __wrapped__)
+    def bound(self, *args, **kwargs):
+        return impl(self, *args, _prev=prev, **kwargs)
+    bound._sugar_amd_regulariser = True
+    bound._sugar_amd_previous = prev
+    return bound
+
+
+def install_regulariser(sugar_model_module, names=REGULARISER_PATCHED):
+    """Bind the four regulariser methods of `sugar_model_module.SuGaR` (see REGULARISER_PATCHED) on top of whatever is bound now: the
+    reference's methods or those of `install`.  Independent of `install`, `install_row_gathers` and `install_binding`, in any order
+    (`install` run afterwards puts its `get_field_values` on top, and that hands the calls implemented here down to this one).
+    What was bound before stays reachable as `SuGaR._sugar_amd_regulariser_original[name]`.  Idempotent; returns the bound names."""
+    cls = sugar_model_module.SuGaR
+    saved = cls.__dict__.get(_REGULARISER_KEY)
+    if saved is None:
+        saved = {}
+        setattr(cls, _REGULARISER_KEY, saved)
+    for name in names:
+        if name in saved:
+            continue
+        prev = getattr(cls, name)
+        reference_method = cls.__dict__.get("_sugar_amd_original", {}).get(name, prev)
+        saved[name] = prev
+        setattr(cls, name, _regulariser_binding(_REGULARISER_IMPL[name], prev, reference_method))
+    return list(saved)
+
+
+def uninstall_regulariser(sugar_model_module):
+    """Undo `install_regulariser` wherever its bindings sit now: on top (rebound to what they replaced), or underneath a binding
+    that `install` made later (that one is re-made over what ours replaced).  Idempotent."""
+    cls = sugar_model_module.SuGaR
+    saved = cls.__dict__.get(_REGULARISER_KEY)
+    if saved is None:
+        return
+    above = cls.__dict__.get("_sugar_amd_original", {})
+    for name, prev in saved.items():
+        if getattr(cls.__dict__.get(name), "_sugar_amd_regulariser", False):
+            setattr(cls, name, prev)
+        elif getattr(above.get(name), "_sugar_amd_regulariser", False):
+            above[name] = prev
+            setattr(cls, name, functools.partialmethod(_IMPL[name], _orig=prev))
+    delattr(cls, _REGULARISER_KEY)
+
+
 def uninstall(sugar_model_module):
+    uninstall_regulariser(sugar_model_module)
     uninstall_binding(sugar_model_module)
     uninstall_row_gathers(sugar_model_module)
     cls = sugar_model_module.SuGaR
