@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Times the four operations of csrc/sdf_regulariser.hip against the torch compositions they replace, on the same GPU in the same
+"""Times the four operations of the SDF regulariser (csrc/sdf_regulariser.hip, the field in csrc/field.hip) against the torch compositions they replace, on the same GPU in the same
 process, at the size of a coarse-stage SDF iteration: N = 1M samples, P = 2M Gaussians, K = 16 neighbours, a 1920 x 1080 depth map.
 
 Per operation and variant: forward and backward time (device events around the call; the backward is `torch.autograd.grad` over the

@@ -39,7 +39,8 @@ SOURCES = {
     "adam.hip": [],
     "activations.hip": [],
     "field.hip": [],
-    "sdf_regulariser.hip": [],  # field.hip's flags: the opacities and densities are the same expressions and must round the same way
+    "group.hip": [],
+    "sdf_regulariser.hip": [],
     "pick.hip": [],
     "capi.hip": [],
     "train.hip": [],

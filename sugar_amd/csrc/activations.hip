@@ -66,7 +66,7 @@ extern "C" int sgr_activations_forward(int P, const float* scaling_raw, const fl
     if (((uintptr_t)rotation_raw | (uintptr_t)rotations) & 15) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_activations_fwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, scaling_raw, rotation_raw,
                        opacity_raw, scales, rotations, opacities);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 extern "C" int sgr_activations_backward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
@@ -81,5 +81,5 @@ extern "C" int sgr_activations_backward(int P, const float* scaling_raw, const f
     hipLaunchKernelGGL(k_activations_bwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, scaling_raw, rotation_raw,
                        opacity_raw, dL_dscales, dL_drotations, dL_dopacities, dL_dscaling_raw, dL_drotation_raw,
                        dL_dopacity_raw);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }

@@ -208,7 +208,7 @@ int sgr_adam_launch(long long n, float* params, const float* grads, float* exp_a
                        reinterpret_cast<const f4*>(grads), reinterpret_cast<f4*>(exp_avg),
                        reinterpret_cast<f4*>(exp_avg_sq), sg, beta1, beta2, sgr_one_minus(beta1), sgr_one_minus(beta2), eps, bc1, bc2_sqrt, grad_scale, extra, extra_n, guard,
                        guard_cap, (int)(n & 3));
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 extern "C" int sgr_adam_step_ex(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,
@@ -265,5 +265,5 @@ extern "C" int sgr_adam_step_multi(int n_tensors, const long long* n, float* con
     a.blk_begin[ADAM_MAX_TENSORS] = blk;
     for (int t = n_tensors; t < ADAM_MAX_TENSORS; t++) a.blk_begin[t] = blk;
     hipLaunchKernelGGL(k_adam_multi, dim3(blk), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }

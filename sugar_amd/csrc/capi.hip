@@ -117,7 +117,7 @@ void SgrStageTimer::stop()
     }
 }
 
-// error reporting for the other translation units (mesh_raster.hip): same thread-local message as sgr_last_error()
+// error reporting for the other translation units (declared in sgr_common.h): same thread-local message as sgr_last_error()
 int sgr_fail(int code, const char* msg) { return fail(code, msg ? msg : ""); }
 
 // process-wide exact-alpha mode (include/sugar_raster.h: sgr_set_exact_alpha): ON unless SGR_EXACT_ALPHA=0 is in the environment

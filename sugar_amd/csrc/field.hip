@@ -6,7 +6,15 @@
 //                   with B_g = R_g diag(1 / max(s_g, 1e-8))  (get_covariance(return_full_matrix, return_sqrt, inverse_scales),
 //                   :730-736).  The reference materialises [N,16,3,3] and [N,16,3,1] temporaries per call; here one lane
 //                   owns one sample and walks its 16 neighbours.
-//   backward      : gradients of sum(g_op * o) + sum(g_den * density) w.r.t. x, mu, B, strength (autograd of the above).
+//   backward      : gradients of sum(g_op * o) + sum(g_den * density) w.r.t. x, mu, B, strength (autograd of the above).  The
+//                   (sample, neighbour) pairs are grouped by Gaussian (csrc/group.hip) and summed in a fixed order.
+//   sdf field     : sugar_scene/sugar_model.py:1247-1307 with beta_mode 'average' (the coarse stage's regulariser,
+//                   sugar_trainers/coarse_sdf.py:566-716): the opacities and density above -- the same kernels, template <bool SDF> -- then
+//                     d' = density < 1 ? density : density / (density + 1e-12)      (the denominator carries no gradient)
+//                     beta = mean_k min_scaling[nbr_k]
+//                     sdf = beta * (sqrt(-2 ln max(d', opacity_min_clamp)) - sqrt(-2 ln min(threshold, 1)))
+//                   Backward: k_sdf_tail_bwd forms the per-sample gradients of density and beta, the density backward's kernels carry
+//                   them on and write dmin_scaling as a fourteenth sum.  Every per-Gaussian row is written, without float atomics.
 //   level sets    : sugar_scene/sugar_model.py:1971-2079 (compute_level_surface_points_from_camera_fast): 21 samples along
 //                   the pixel's ray in +-3 sigma of the front Gaussian, density at each (normalised where >= 1), first
 //                   crossing per level with linear interpolation, normal = -normalize(grad density) at the crossing.
@@ -66,39 +74,73 @@ __device__ __forceinline__ void bt_mul(const float* Bm, float dx, float dy, floa
     w2 = Bm[2] * dx + Bm[5] * dy + Bm[8] * dz;
 }
 
-// sum over the 16 lanes of a DPP row, returned to every lane of the row (row_ror:8 / 4 / 2 / 1 fold into the adds)
-__device__ __forceinline__ float row_sum16(float x)
+// ---- the SDF of the coarse stage's regulariser (sugar_model.py:1247-1307, beta_mode 'average') on top of the density -----------------
+struct TailArgs { float clamp_min, offset; };  // opacity_min_clamp; sqrt(-2 ln min(threshold, 1))
+
+TailArgs tail_args(float density_threshold, float opacity_min_clamp)
 {
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x128, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x124, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x122, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x121, 0xF, 0xF, false));
-    return x;
+    const double th = density_threshold < 1.f ? (double)density_threshold : 1.0;
+    return TailArgs{opacity_min_clamp, (float)sqrt(-2.0 * log(th))};   // (np.sqrt(-2 np.log(min(threshold, 1))), then float32)
 }
+
+__device__ __forceinline__ void sdf_tail(float density, float beta_sum, int K, const TailArgs ta, float& beta, float& sdf)
+{
+    const float dprime = density < 1.f ? density : density / (density + 1e-12f);
+    const float cl = fmaxf(dprime, ta.clamp_min);
+    beta = beta_sum / (float)K;
+    sdf = beta * (sqrtf(-2.f * logf(cl)) - ta.offset);
+}
+
+// ---- the kernel family: template <bool SDF> ---------------------------------------------------------------------------------------
+// SDF = false is the density field (sgr_density_field_*): the indices are trusted (the entry points have no P), the arguments
+// P, min_scaling, ta, beta, sdf, gB and dmin_scaling are not read.  SDF = true is the SDF field (sgr_sdf_field_*): the same pair
+// arithmetic from the same text -- the forward's opacities and densities are the density field's bit for bit
+// (tests/test_gpu_field.py: test_sdf_field_carries_the_density_fields_bits; the backward's dx and dstrengths are not) -- and around it
+//   * the index wraps once and a neighbour outside [0, P) contributes nothing;
+//   * the forward sums min_scaling over the neighbours and appends sdf_tail;
+//   * the backward reads the per-sample gradients that k_sdf_tail_bwd formed (g_den = gD, never NULL; gB) and writes dmin_scaling.
 
 // K == 16 (SuGaR's neighbour count): a lane per (sample, neighbour) PAIR, the sixteen pairs of a sample in one DPP row.  The
 // lane-per-sample loops below issue their sixteen record gathers one after the other (each waits for its index): 0.54 ms for 16M pairs
 // against records that fit the L2; with a lane per pair all gathers of a wave are in flight at once.
-__global__ void __launch_bounds__(256) k_density_fwd16(long long NK, const float* __restrict__ x, const long long* __restrict__ nbr,
+template <bool SDF>
+__global__ void __launch_bounds__(256) k_density_fwd16(long long NK, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
                                                        const float* __restrict__ centers, const float* __restrict__ B,
-                                                       const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
-                                                       float* __restrict__ opac, float* __restrict__ density)
+                                                       const float* __restrict__ strengths, const float4* __restrict__ packed,
+                                                       const float* __restrict__ min_scaling, float factor, TailArgs ta,
+                                                       float* __restrict__ opac, float* __restrict__ density, float* __restrict__ beta,
+                                                       float* __restrict__ sdf)
 {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= NK) return;   // (NK is a multiple of 16: rows leave whole)
     const size_t n = (size_t)(p >> 4);
-    const GaussNbr g = load_nbr(nbr[p], centers, B, strengths, packed);
+    // (the forward runs its pair arithmetic for EVERY lane, on record 0 where the SDF index is out of range, and discards that lane's
+    // result: under a divergent branch the compiler pairs the products into packed FP32 and the opacities lose the density field's bits)
+    const long long gi = SDF ? wrap_row(nbr[p], P) : nbr[p];
+    const bool in = !SDF || (gi >= 0 && gi < P);
+    const GaussNbr g = load_nbr(in ? gi : 0, centers, B, strengths, packed);
     float w0, w1, w2;
     bt_mul(g.B, x[3 * n] - g.mx, x[3 * n + 1] - g.my, x[3 * n + 2] - g.mz, w0, w1, w2);
     const float q = fminf(fmaxf(w0 * w0 + w1 * w1 + w2 * w2, 0.f), 1e8f);
-    const float o = factor * g.s * __expf(-0.5f * q);
+    float o = factor * g.s * __expf(-0.5f * q), ms = 0.f;
+    if constexpr (SDF) { o = in ? o : 0.f; ms = in ? min_scaling[gi] : 0.f; }
     if (opac) opac[p] = o;
     const float sum = row_sum16(o);
-    if ((threadIdx.x & 15) == 0) density[n] = sum;
+    if constexpr (SDF) {
+        const float bsum = row_sum16(ms);
+        if ((threadIdx.x & 15) == 0) {
+            float b, s;
+            sdf_tail(sum, bsum, 16, ta, b, s);
+            density[n] = sum; beta[n] = b; sdf[n] = s;
+        }
+    } else {
+        if ((threadIdx.x & 15) == 0) density[n] = sum;
+    }
 }
 
 // the gradient of the sample positions, same mapping (the per-Gaussian gradients are the gather kernel's)
-__global__ void __launch_bounds__(256) k_density_dx16(long long NK, const float* __restrict__ x, const long long* __restrict__ nbr,
+template <bool SDF>
+__global__ void __launch_bounds__(256) k_density_dx16(long long NK, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
                                                       const float* __restrict__ centers, const float* __restrict__ B,
                                                       const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
                                                       const float* __restrict__ g_opac, const float* __restrict__ g_den,
@@ -107,40 +149,90 @@ __global__ void __launch_bounds__(256) k_density_dx16(long long NK, const float*
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= NK) return;
     const size_t n = (size_t)(p >> 4);
-    const GaussNbr g = load_nbr(nbr[p], centers, B, strengths, packed);
-    float w0, w1, w2;
-    bt_mul(g.B, x[3 * n] - g.mx, x[3 * n + 1] - g.my, x[3 * n + 2] - g.mz, w0, w1, w2);
-    const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
-    const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-    const float go = (g_opac ? g_opac[p] : 0.f) + (g_den ? g_den[n] : 0.f);
-    const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
-    const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
-    const float ax = row_sum16(g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2);
-    const float ay = row_sum16(g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2);
-    const float az = row_sum16(g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2);
+    const long long gi = SDF ? wrap_row(nbr[p], P) : nbr[p];
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    if (!SDF || (gi >= 0 && gi < P)) {
+        const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
+        float w0, w1, w2;
+        bt_mul(g.B, x[3 * n] - g.mx, x[3 * n + 1] - g.my, x[3 * n + 2] - g.mz, w0, w1, w2);
+        const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
+        const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
+        const float go = (g_opac ? g_opac[p] : 0.f) + ((SDF || g_den) ? g_den[n] : 0.f);
+        const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
+        const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
+        ax = g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
+        ay = g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
+        az = g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
+    }
+    ax = row_sum16(ax); ay = row_sum16(ay); az = row_sum16(az);
     if ((threadIdx.x & 15) == 0) { dx_out[3 * n] = ax; dx_out[3 * n + 1] = ay; dx_out[3 * n + 2] = az; }
 }
 
-__global__ void __launch_bounds__(256) k_density_fwd(int N, int K, const float* __restrict__ x, const long long* __restrict__ nbr,
+// any K: a lane per sample
+template <bool SDF>
+__global__ void __launch_bounds__(256) k_density_fwd(int N, int K, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
                                                      const float* __restrict__ centers, const float* __restrict__ B,
-                                                     const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
-                                                     float* __restrict__ opac, float* __restrict__ density)
+                                                     const float* __restrict__ strengths, const float4* __restrict__ packed,
+                                                     const float* __restrict__ min_scaling, float factor, TailArgs ta,
+                                                     float* __restrict__ opac, float* __restrict__ density, float* __restrict__ beta,
+                                                     float* __restrict__ sdf)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     const float px = x[3 * (size_t)n], py = x[3 * (size_t)n + 1], pz = x[3 * (size_t)n + 2];
-    float sum = 0.f;
+    float sum = 0.f, bsum = 0.f;
     for (int k = 0; k < K; k++) {
-        const GaussNbr g = load_nbr(nbr[(size_t)n * K + k], centers, B, strengths, packed);
+        const long long gi = SDF ? wrap_row(nbr[(size_t)n * K + k], P) : nbr[(size_t)n * K + k];
+        const bool in = !SDF || (gi >= 0 && gi < P);
+        const GaussNbr g = load_nbr(in ? gi : 0, centers, B, strengths, packed);
         float w0, w1, w2;
         bt_mul(g.B, px - g.mx, py - g.my, pz - g.mz, w0, w1, w2);
         const float q = fminf(fmaxf(w0 * w0 + w1 * w1 + w2 * w2, 0.f), 1e8f);
-        const float o = factor * g.s * __expf(-0.5f * q);
+        float o = factor * g.s * __expf(-0.5f * q);
+        if constexpr (SDF) { o = in ? o : 0.f; bsum += in ? min_scaling[gi] : 0.f; }
         if (opac) opac[(size_t)n * K + k] = o;
         sum += o;
     }
+    if constexpr (SDF) {
+        float b, s;
+        sdf_tail(sum, bsum, K, ta, b, s);
+        beta[n] = b; sdf[n] = s;
+    }
     density[n] = sum;
 }
+
+template <bool SDF>
+__global__ void __launch_bounds__(256) k_density_dx(int N, int K, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
+                                                    const float* __restrict__ centers, const float* __restrict__ B,
+                                                    const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
+                                                    const float* __restrict__ g_opac, const float* __restrict__ g_den,
+                                                    float* __restrict__ dx_out)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const float px = x[3 * (size_t)n], py = x[3 * (size_t)n + 1], pz = x[3 * (size_t)n + 2];
+    const float gd = (SDF || g_den) ? g_den[n] : 0.f;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int k = 0; k < K; k++) {
+        const size_t p = (size_t)n * K + k;
+        const long long gi = SDF ? wrap_row(nbr[p], P) : nbr[p];
+        if (SDF && (gi < 0 || gi >= P)) continue;
+        const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
+        float w0, w1, w2;
+        bt_mul(g.B, px - g.mx, py - g.my, pz - g.mz, w0, w1, w2);
+        const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
+        const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
+        const float go = (g_opac ? g_opac[p] : 0.f) + gd;
+        const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
+        const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
+        ax += g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
+        ay += g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
+        az += g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
+    }
+    dx_out[3 * (size_t)n] = ax; dx_out[3 * (size_t)n + 1] = ay; dx_out[3 * (size_t)n + 2] = az;
+}
+
+// ---- the atomics formulation of the backward, kept for comparison (_DensityField.use_gather = False) -------------------------------
 
 __global__ void __launch_bounds__(256) k_density_bwd(int N, int K, const float* __restrict__ x, const long long* __restrict__ nbr,
                                                      const float* __restrict__ centers, const float* __restrict__ B,
@@ -186,246 +278,16 @@ __global__ void __launch_bounds__(256) k_density_bwd(int N, int K, const float* 
 
 // ---- gather formulation of the backward ---------------------------------------------------------------------------
 // The kernel above spends 13 float atomics per (sample, neighbour) pair (208 M at 1M x 16: ~10 ms, L2 atomic rate).  Here the
-// pairs are first laid out per Gaussian -- by launch_group_by_key below (stable radix grouping; until the end of round 4, and with
-// SGR_GROUP_ATOMICS=1, by ONE returning integer atomic per pair for its rank, a scan and a fill) -- and sixteen lanes per Gaussian
-// then sum its pairs in registers and write its 13 outputs once.  This kernel: the gradient of the sample positions (a lane per
-// sample), plus the ranks in the atomics mode (cnt != NULL).
-__global__ void __launch_bounds__(256) k_density_bwd_rank(int N, int K, const float* __restrict__ x, const long long* __restrict__ nbr,
-                                                          const float* __restrict__ centers, const float* __restrict__ B,
-                                                          const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
-                                                          const float* __restrict__ g_opac, const float* __restrict__ g_den,
-                                                          float* __restrict__ dx_out, uint32_t* __restrict__ cnt,
+// pairs are first laid out per Gaussian -- by sgr_group_by_key (group.hip: stable radix grouping; until the end of round 4, and with
+// SGR_GROUP_ATOMICS=1, by ONE returning integer atomic per pair for its rank, a scan and a fill: the two kernels below) -- and sixteen
+// lanes per Gaussian then sum its pairs in registers and write its 13 outputs once.  The gradient of the sample positions is
+// k_density_dx16 / k_density_dx above.
+__global__ void __launch_bounds__(256) k_density_bwd_rank(long long NK, const long long* __restrict__ nbr, uint32_t* __restrict__ cnt,
                                                           uint32_t* __restrict__ rank)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float px = x[3 * (size_t)n], py = x[3 * (size_t)n + 1], pz = x[3 * (size_t)n + 2];
-    const float gd = g_den ? g_den[n] : 0.f;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int k = 0; k < K; k++) {
-        const size_t p = (size_t)n * K + k;
-        const long long gi = nbr[p];
-        if (cnt) rank[p] = atomicAdd(&cnt[gi], 1u);   // (cnt == NULL: the pairs are grouped by launch_group_by_key instead)
-        if (dx_out) {
-            const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
-            float w0, w1, w2;
-            bt_mul(g.B, px - g.mx, py - g.my, pz - g.mz, w0, w1, w2);
-            const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
-            const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-            const float go = (g_opac ? g_opac[p] : 0.f) + gd;
-            const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
-            const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
-            ax += g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
-            ay += g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
-            az += g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
-        }
-    }
-    if (dx_out) { dx_out[3 * (size_t)n] = ax; dx_out[3 * (size_t)n + 1] = ay; dx_out[3 * (size_t)n + 2] = az; }
-}
-
-// exclusive scan of cnt[0..n) into start[0..n], start[n] = total: block sums, scan of the block sums, block-local scans
-#define FSCAN_BLOCK 2048  // elements per 256-thread workgroup (8 per thread)
-__global__ void __launch_bounds__(256) k_fscan_sums(int n, const uint32_t* __restrict__ cnt, uint32_t* __restrict__ block_sums)
-{
-    __shared__ uint32_t s_w[4];
-    const int base = blockIdx.x * FSCAN_BLOCK + threadIdx.x * 8;
-    uint32_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) sum += (base + i < n) ? cnt[base + i] : 0u;
-    for (int o = 32; o > 0; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(1024) k_fscan_top(int n_blocks, uint32_t* __restrict__ block_sums, uint32_t* __restrict__ total)
-{
-    __shared__ uint32_t s_part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n_blocks + 1023) / 1024;
-    const int b = tid * per, e = min(n_blocks, b + per);
-    uint32_t sum = 0;
-    for (int i = b; i < e; i++) sum += block_sums[i];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t v = (tid >= o) ? s_part[tid - o] : 0;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
-    for (int i = b; i < e; i++) { const uint32_t v = block_sums[i]; block_sums[i] = run; run += v; }
-    if (tid == 1023) *total = s_part[1023];
-}
-
-__global__ void __launch_bounds__(256) k_fscan_apply(int n, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ block_sums,
-                                                     uint32_t* __restrict__ start)
-{
-    __shared__ uint32_t s_w[4];
-    const int base = blockIdx.x * FSCAN_BLOCK + threadIdx.x * 8;
-    uint32_t v[8], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { v[i] = (base + i < n) ? cnt[base + i] : 0u; sum += v[i]; }
-    uint32_t run;
-    sgr_block_scan<4>(sum, s_w, run);
-    run += block_sums[blockIdx.x];
-#pragma unroll
-    for (int i = 0; i < 8; i++) { if (base + i < n) start[base + i] = run; run += v[i]; }
-}
-
-// ---- stable grouping of M entries by a small integer key: LSD radix sort, 8 bits per pass, ranks formed in LDS -----------------------
-// Replaces "one returning integer atomic per entry for its rank" (16M of them per call in a trainer's SDF phase: ~20 G atomics/s whatever
-// the contention, 0.85 ms) and makes the order of the entries inside a group -- hence of the float additions that follow -- the
-// order of the entries themselves: the backward is reproducible run to run.
-//   per pass: k_grp_hist (digit counts per chunk of 2048 entries, LDS atomics) -> exclusive scan over [digit][chunk] (k_fscan_*) ->
-//             k_grp_scatter (each wave ranks its 64 entries per digit with eight ballots; one leader lane per (unit, digit) publishes
-//             the unit's count, thread d scans digit d over the chunk's 32 units (8 rounds x 4 waves), entries go to offset + rank)
-//   then    : k_grp_bounds  start[g] = first sorted position whose key is >= g   (binary search; keys past P-1 are the ignored entries)
-#define GRP_CHUNK 2048
-#define GRP_ROUNDS 8
-#define GRP_UNITS (GRP_ROUNDS * 4)
-
-__device__ __forceinline__ uint32_t grp_key64(long long k, int P)  // Python-style wrap once; anything else -> the sentinel P
-{
-    if (k < 0) k += P;
-    return (k >= 0 && k < P) ? (uint32_t)k : (uint32_t)P;
-}
-
-template <bool FIRST>
-__global__ void __launch_bounds__(256) k_grp_hist(long long M, const long long* __restrict__ keys64, const uint32_t* __restrict__ key_in,
-                                                  int P, int shift, uint32_t n_chunks, uint32_t* __restrict__ hist)
-{
-    __shared__ uint32_t s_h[256];
-    const int tid = threadIdx.x;
-    s_h[tid] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * GRP_CHUNK;
-#pragma unroll
-    for (int r = 0; r < GRP_ROUNDS; r++) {
-        const long long i = base + r * 256 + tid;
-        if (i < M) {
-            const uint32_t key = FIRST ? grp_key64(keys64[i], P) : key_in[i];
-            atomicAdd(&s_h[(key >> shift) & 255u], 1u);
-        }
-    }
-    __syncthreads();
-    hist[(size_t)tid * n_chunks + blockIdx.x] = s_h[tid];
-}
-
-template <bool FIRST>
-__global__ void __launch_bounds__(256) k_grp_scatter(long long M, const long long* __restrict__ keys64, const uint32_t* __restrict__ key_in,
-                                                     const uint32_t* __restrict__ val_in, int P, int shift, uint32_t n_chunks,
-                                                     const uint32_t* __restrict__ offs, uint32_t* __restrict__ key_out,
-                                                     uint32_t* __restrict__ val_out)
-{
-    __shared__ uint32_t s_u[GRP_UNITS * 256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < GRP_UNITS * 256; i += 256) s_u[i] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * GRP_CHUNK;
-    uint32_t key[GRP_ROUNDS], val[GRP_ROUNDS], rk[GRP_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < GRP_ROUNDS; r++) {
-        const long long i = base + r * 256 + tid;
-        const bool valid = i < M;
-        key[r] = valid ? (FIRST ? grp_key64(keys64[i], P) : key_in[i]) : 0u;
-        val[r] = valid ? (FIRST ? (uint32_t)i : val_in[i]) : 0u;
-        const uint32_t d = (key[r] >> shift) & 255u;
-        unsigned long long mask = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long bb = __ballot(bit);
-            mask &= bit ? bb : ~bb;
-        }
-        const unsigned long long below = mask & ((1ull << lane) - 1ull);
-        rk[r] = (uint32_t)__popcll(below);
-        if (valid && below == 0ull) s_u[(r * 4 + wave) * 256 + d] = (uint32_t)__popcll(mask);  // the group's first lane publishes its size
-    }
-    __syncthreads();
-    {
-        uint32_t run = offs[(size_t)tid * n_chunks + blockIdx.x];
-#pragma unroll 8
-        for (int u = 0; u < GRP_UNITS; u++) {
-            const uint32_t t = s_u[u * 256 + tid];
-            s_u[u * 256 + tid] = run;
-            run += t;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < GRP_ROUNDS; r++) {
-        const long long i = base + r * 256 + tid;
-        if (i < M) {
-            const uint32_t d = (key[r] >> shift) & 255u;
-            const uint32_t pos = s_u[(r * 4 + wave) * 256 + d] + rk[r];
-            key_out[pos] = key[r];
-            val_out[pos] = val[r];
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_grp_bounds(int P, long long M, const uint32_t* __restrict__ sorted_keys, uint32_t* __restrict__ start)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g > P) return;
-    long long lo = 0, hi = M;   // first position with key >= g
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted_keys[mid] < (uint32_t)g) lo = mid + 1; else hi = mid;
-    }
-    start[g] = (uint32_t)lo;
-}
-
-struct GroupScratch { uint32_t *key_a, *val_a, *key_b, *val_b, *hist, *offs, *block_sums; size_t total; };
-GroupScratch carve_group(char* base, size_t M)
-{
-    GroupScratch g;
-    const size_t n_chunks = (M + GRP_CHUNK - 1) / GRP_CHUNK, H = 256 * (n_chunks ? n_chunks : 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { uint32_t* p = reinterpret_cast<uint32_t*>(base + off); off = sgr_align(off + bytes); return p; };
-    g.key_a = take(M * 4); g.val_a = take(M * 4); g.key_b = take(M * 4); g.val_b = take(M * 4);
-    g.hist = take((H + 1) * 4); g.offs = take((H + 1) * 4); g.block_sums = take(((H + FSCAN_BLOCK - 1) / FSCAN_BLOCK + 2) * 4);
-    g.total = off;
-    return g;
-}
-
-// groups the M entries of keys64 (values in [-P, P); others are left out) by key: *list_out = entry numbers, key-major, ascending
-// inside a key; start[0..P] = offsets into it.  Enqueued on s; no host synchronisation.
-int launch_group_by_key(long long M, const long long* keys64, int P, char* scratch, uint32_t* start, const uint32_t** list_out, hipStream_t s)
-{
-    const GroupScratch g = carve_group(scratch, (size_t)M);
-    const uint32_t n_chunks = (uint32_t)(((size_t)M + GRP_CHUNK - 1) / GRP_CHUNK);
-    const size_t H = 256 * (size_t)n_chunks;
-    const int n_blocks = (int)((H + FSCAN_BLOCK - 1) / FSCAN_BLOCK);
-    int bits = 0;
-    while (bits < 32 && ((unsigned long long)P >> bits) != 0ull) bits++;   // P itself (the sentinel) must fit
-    const int passes = (bits + 7) / 8 > 0 ? (bits + 7) / 8 : 1;
-    uint32_t *kin = nullptr, *vin = nullptr, *kout = g.key_a, *vout = g.val_a;
-    for (int pass = 0; pass < passes; pass++) {
-        const int shift = 8 * pass;
-        if (pass == 0) hipLaunchKernelGGL(k_grp_hist<true>, dim3(n_chunks), dim3(256), 0, s, M, keys64, kin, P, shift, n_chunks, g.hist);
-        else hipLaunchKernelGGL(k_grp_hist<false>, dim3(n_chunks), dim3(256), 0, s, M, keys64, kin, P, shift, n_chunks, g.hist);
-        hipLaunchKernelGGL(k_fscan_sums, dim3(n_blocks), dim3(256), 0, s, (int)H, g.hist, g.block_sums);
-        hipLaunchKernelGGL(k_fscan_top, dim3(1), dim3(1024), 0, s, n_blocks, g.block_sums, g.offs + H);
-        hipLaunchKernelGGL(k_fscan_apply, dim3(n_blocks), dim3(256), 0, s, (int)H, g.hist, g.block_sums, g.offs);
-        if (pass == 0) hipLaunchKernelGGL(k_grp_scatter<true>, dim3(n_chunks), dim3(256), 0, s, M, keys64, kin, vin, P, shift, n_chunks, g.offs, kout, vout);
-        else hipLaunchKernelGGL(k_grp_scatter<false>, dim3(n_chunks), dim3(256), 0, s, M, keys64, kin, vin, P, shift, n_chunks, g.offs, kout, vout);
-        kin = kout; vin = vout;
-        kout = (kin == g.key_a) ? g.key_b : g.key_a;
-        vout = (vin == g.val_a) ? g.val_b : g.val_a;
-    }
-    hipLaunchKernelGGL(k_grp_bounds, dim3((unsigned)((P + 1 + 255) / 256)), dim3(256), 0, s, P, M, kin, start);
-    *list_out = vin;
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
-}
-
-// SGR_GROUP_ATOMICS=1: the round-4 grouping by returning atomics (same-box A/B)
-bool group_by_atomics()
-{
-    static const bool v = [] { const char* e = getenv("SGR_GROUP_ATOMICS"); return e && e[0] == '1'; }();
-    return v;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= NK) return;
+    rank[p] = atomicAdd(&cnt[nbr[p]], 1u);
 }
 
 __global__ void __launch_bounds__(256) k_density_bwd_fill(long long NK, const long long* __restrict__ nbr,
@@ -437,22 +299,24 @@ __global__ void __launch_bounds__(256) k_density_bwd_fill(long long NK, const lo
     pair_list[start[nbr[p]] + rank[p]] = (uint32_t)p;
 }
 
-// SIXTEEN lanes (one DPP row) per Gaussian: they stride over its pairs and fold their 13 partial sums with row rotates.  (One lane
-// per Gaussian, until round 4, walked its list alone -- 280 dependent gathers on average when 1M samples x 16 neighbours meet 57k
-// Gaussians, on 900 waves: 2.0 ms; a trainer's SDF phase has exactly that shape.)
+// SIXTEEN lanes (one DPP row) per Gaussian: they stride over its pairs and fold their 13 partial sums with row rotates (SDF: and
+// dmin_scaling as the fourteenth).  (One lane per Gaussian, until round 4, walked its list alone -- 280 dependent gathers on average
+// when 1M samples x 16 neighbours meet 57k Gaussians, on 900 waves: 2.0 ms; a trainer's SDF phase has exactly that shape.)
+template <bool SDF>
 __global__ void __launch_bounds__(256) k_density_bwd_gather(int P, int K, const float* __restrict__ x,
                                                             const float* __restrict__ centers, const float* __restrict__ B,
                                                             const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
                                                             const float* __restrict__ g_opac, const float* __restrict__ g_den,
-                                                            const uint32_t* __restrict__ start,
+                                                            const float* __restrict__ gB, const uint32_t* __restrict__ start,
                                                             const uint32_t* __restrict__ pair_list, float* __restrict__ dcenters,
-                                                            float* __restrict__ dB, float* __restrict__ dstrengths)
+                                                            float* __restrict__ dB, float* __restrict__ dstrengths,
+                                                            float* __restrict__ dmin_scaling)
 {
     const int t = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) >> 4);
     const uint32_t sub = threadIdx.x & 15;
     if (t >= P) return;   // (whole rows leave together: the row rotates below never cross a row)
     const GaussNbr g = load_nbr(t, centers, B, strengths, packed);
-    float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, ds = 0.f;
+    float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, ds = 0.f, dm = 0.f;
     float b[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) b[i] = 0.f;
@@ -465,8 +329,9 @@ __global__ void __launch_bounds__(256) k_density_bwd_gather(int P, int K, const 
         bt_mul(g.B, dx, dy, dz, w0, w1, w2);
         const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
         const float ex = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-        const float go = (g_opac ? g_opac[p] : 0.f) + (g_den ? g_den[n] : 0.f);
+        const float go = (g_opac ? g_opac[p] : 0.f) + ((SDF || g_den) ? g_den[n] : 0.f);
         ds += go * factor * ex;
+        if constexpr (SDF) dm += gB[n];
         const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * ex * go : 0.f;
         const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
         dc0 -= g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
@@ -477,11 +342,13 @@ __global__ void __launch_bounds__(256) k_density_bwd_gather(int P, int K, const 
         b[6] += dz * dw0; b[7] += dz * dw1; b[8] += dz * dw2;
     }
     dc0 = row_sum16(dc0); dc1 = row_sum16(dc1); dc2 = row_sum16(dc2); ds = row_sum16(ds);
+    if constexpr (SDF) dm = row_sum16(dm);
 #pragma unroll
     for (int i = 0; i < 9; i++) b[i] = row_sum16(b[i]);
     if (sub == 0) {
         dcenters[3 * (size_t)t] = dc0; dcenters[3 * (size_t)t + 1] = dc1; dcenters[3 * (size_t)t + 2] = dc2;
         dstrengths[t] = ds;
+        if constexpr (SDF) dmin_scaling[t] = dm;
     }
     if (sub < 9) {   // nine lanes store the nine entries of dB (each holds all the sums)
         float v = b[0];
@@ -491,67 +358,33 @@ __global__ void __launch_bounds__(256) k_density_bwd_gather(int P, int K, const 
     }
 }
 
-// ---- out[p, :] = sum over { n : idx[n] == p } of src[n, :]  -- the backward of a row gather `x[idx]` --------------------------------
-// What autograd runs for every `tensor[index]` of the regulariser (sugar_model.py:922-925: points / quaternions / scaling of 1M sampled
-// Gaussians; coarse_sdf.py:690-692: the normals of 1M x 16 neighbours): stock PyTorch sorts the indices and reduces segments, 1.3 ms per
-// call on average and six calls per iteration.  Same scheme as the density backward above: the entries are grouped by row
-// (launch_group_by_key; k_rows_rank / k_rows_fill are the SGR_GROUP_ATOMICS=1 variant), sixteen lanes per row add its entries up.
-// Negative indices wrap once (Python semantics); entries outside [-P, P) are ignored.
-__device__ __forceinline__ long long rows_wrap(long long i, int P) { return i < 0 ? i + P : i; }
-
-__global__ void __launch_bounds__(256) k_rows_rank(long long N, const long long* __restrict__ idx, int P, uint32_t* __restrict__ cnt,
-                                                   uint32_t* __restrict__ rank)
+// per sample: the gradient that reaches the density (its own plus the sdf's, through the tail in the reference's operation order:
+// mul, sqrt, mul by -2, log, clamp, the division of the rows >= 1) and the gradient per neighbour of min_scaling (beta's / K).
+// Rows with density >= 1 carry what float32 autograd gives there (sqrt(0): non-finite).
+__global__ void __launch_bounds__(256) k_sdf_tail_bwd(int N, int K, const float* __restrict__ density, const float* __restrict__ beta,
+                                                      const float* __restrict__ g_den, const float* __restrict__ g_beta,
+                                                      const float* __restrict__ g_sdf, TailArgs ta, float* __restrict__ gD,
+                                                      float* __restrict__ gB)
 {
-    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    const long long g = rows_wrap(idx[n], P);
-    if (g >= 0 && g < P) rank[n] = atomicAdd(&cnt[g], 1u);
-}
-
-__global__ void __launch_bounds__(256) k_rows_fill(long long N, const long long* __restrict__ idx, int P, const uint32_t* __restrict__ start,
-                                                   const uint32_t* __restrict__ rank, uint32_t* __restrict__ list)
-{
-    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const long long g = rows_wrap(idx[n], P);
-    if (g >= 0 && g < P) list[start[g] + rank[n]] = (uint32_t)n;
-}
-
-template <int W>
-__global__ void __launch_bounds__(256) k_rows_gather(int P, const float* __restrict__ src, const uint32_t* __restrict__ start,
-                                                     const uint32_t* __restrict__ list, float* __restrict__ out)
-{
-    const int t = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) >> 4);
-    const uint32_t sub = threadIdx.x & 15;
-    if (t >= P) return;
-    float acc[W];
-#pragma unroll
-    for (int c = 0; c < W; c++) acc[c] = 0.f;
-    const uint32_t e0 = start[t], e1 = start[t + 1];
-    for (uint32_t e = e0 + sub; e < e1; e += 16) {
-        const float* r = src + (size_t)list[e] * W;
-#pragma unroll
-        for (int c = 0; c < W; c++) acc[c] += r[c];
+    const float D = density[n];
+    const bool over = !(D < 1.f);
+    const float dprime = over ? D / (D + 1e-12f) : D;
+    const float cl = fmaxf(dprime, ta.clamp_min);
+    const float r = sqrtf(-2.f * logf(cl));
+    float gd = g_den ? g_den[n] : 0.f, gb = g_beta ? g_beta[n] : 0.f;
+    if (g_sdf) {
+        const float gs = g_sdf[n];
+        gb += gs * (r - ta.offset);
+        const float gr = gs * beta[n];
+        const float gL = gr / (2.f * r);
+        float gcl = (gL * -2.f) / cl;
+        if (!(dprime >= ta.clamp_min)) gcl = 0.f;      // clamp(min): the gradient passes where the input is >= min
+        gd += over ? gcl / (D + 1e-12f) : gcl;
     }
-#pragma unroll
-    for (int c = 0; c < W; c++) acc[c] = row_sum16(acc[c]);
-    if (sub < (uint32_t)W) {
-        float v = acc[0];
-#pragma unroll
-        for (int c = 1; c < W; c++) v = (sub == (uint32_t)c) ? acc[c] : v;
-        out[(size_t)t * W + sub] = v;
-    }
-}
-
-// ---- SuGaR.get_covariance(return_sqrt=True[, inverse_scales=True]), sugar_scene/sugar_model.py:730-736 ---------------------
-// out[a][b] = R(q)[a][b] * s[b],  R = pytorch3d's quaternion_to_matrix (real part first, two_s = 2 / |q|^2: any non-zero q),
-// s = scaling or 1 / clamp(scaling, 1e-8).  The reference builds it with ~25 elementwise launches (plus autograd twins) every
-// time the regulariser or the level-set sampler runs.
-__device__ __forceinline__ void quat_M(float r, float i, float j, float k, float M[9])
-{
-    M[0] = -(j * j + k * k); M[1] = i * j - k * r;     M[2] = i * k + j * r;
-    M[3] = i * j + k * r;    M[4] = -(i * i + k * k);  M[5] = j * k - i * r;
-    M[6] = i * k - j * r;    M[7] = j * k + i * r;     M[8] = -(i * i + j * j);
+    gD[n] = gd;
+    gB[n] = gb / (float)K;
 }
 
 // the depth render's colours (sugar_model.py:1901-1911): every Gaussian's view-space z three times (`depth.expand(-1, 3)`), from the
@@ -626,6 +459,10 @@ __global__ void __launch_bounds__(256) k_unproject_pixels(int n, const int64_t* 
     world[3 * (size_t)t + 2] = xc * i02 + yc * i12 + z * i22 + i32;
 }
 
+// ---- SuGaR.get_covariance(return_sqrt=True[, inverse_scales=True]), sugar_scene/sugar_model.py:730-736 ---------------------
+// out[a][b] = R(q)[a][b] * s[b],  R = pytorch3d's quaternion_to_matrix (real part first, two_s = 2 / |q|^2: any non-zero q; quat_M of
+// sgr_device.h), s = scaling or 1 / clamp(scaling, 1e-8).  The reference builds it with ~25 elementwise launches (plus autograd twins)
+// every time the regulariser or the level-set sampler runs.
 __global__ void __launch_bounds__(256) k_scaled_rotation_fwd(int P, const float* __restrict__ quats, const float* __restrict__ scaling,
                                                              int inverse, float* __restrict__ out)
 {
@@ -775,14 +612,33 @@ __global__ void __launch_bounds__(128) k_level_set(int N, int K, const float* __
     }
 }
 
-}  // namespace
-
-// the stable grouping above with external linkage, for csrc/sdf_regulariser.hip (declared in sgr_group.h)
-size_t sgr_group_scratch_bytes(size_t M) { return carve_group(nullptr, M).total; }
-int sgr_group_by_key(long long M, const long long* keys64, int P, char* scratch, uint32_t* start, const uint32_t** list_out, hipStream_t s)
+// the forward and the gradient of the sample positions: a lane per pair when K == 16, else a lane per sample
+template <bool SDF>
+void launch_fwd(int N, int K, int P, const float* x, const long long* nbr, const float* centers, const float* B, const float* strengths,
+                const float4* packed, const float* min_scaling, float factor, TailArgs ta, float* opac, float* density, float* beta,
+                float* sdf, hipStream_t s)
 {
-    return launch_group_by_key(M, keys64, P, scratch, start, list_out, s);
+    if (K == 16)
+        hipLaunchKernelGGL(k_density_fwd16<SDF>, dim3(blocks256((size_t)N * 16)), dim3(256), 0, s, (long long)N * 16, P, x, nbr, centers, B,
+                           strengths, packed, min_scaling, factor, ta, opac, density, beta, sdf);
+    else
+        hipLaunchKernelGGL(k_density_fwd<SDF>, dim3(blocks256((size_t)N)), dim3(256), 0, s, N, K, P, x, nbr, centers, B, strengths, packed,
+                           min_scaling, factor, ta, opac, density, beta, sdf);
 }
+
+template <bool SDF>
+void launch_dx(int N, int K, int P, const float* x, const long long* nbr, const float* centers, const float* B, const float* strengths,
+               const float4* packed, float factor, const float* g_opac, const float* g_den, float* dx_out, hipStream_t s)
+{
+    if (K == 16)
+        hipLaunchKernelGGL(k_density_dx16<SDF>, dim3(blocks256((size_t)N * 16)), dim3(256), 0, s, (long long)N * 16, P, x, nbr, centers, B,
+                           strengths, packed, factor, g_opac, g_den, dx_out);
+    else
+        hipLaunchKernelGGL(k_density_dx<SDF>, dim3(blocks256((size_t)N)), dim3(256), 0, s, N, K, P, x, nbr, centers, B, strengths, packed,
+                           factor, g_opac, g_den, dx_out);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -792,17 +648,25 @@ int sgr_density_field_forward(int N, int K, const float* x, const int64_t* nbr_i
 {
     if (N <= 0) return 0;
     if (K <= 0 || !x || !nbr_idx || !centers || !inv_scaled_rot || !strengths || !density) return SGR_E_INVALID;
-    if (K == 16) {
-        const long long nk = (long long)N * 16;
-        hipLaunchKernelGGL(k_density_fwd16, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nk, x,
-                           reinterpret_cast<const long long*>(nbr_idx), centers, inv_scaled_rot, strengths, reinterpret_cast<const float4*>(packed),
-                           density_factor, neighbor_opacities, density);
-    } else {
-        hipLaunchKernelGGL(k_density_fwd, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, K, x,
-                           reinterpret_cast<const long long*>(nbr_idx), centers, inv_scaled_rot, strengths, reinterpret_cast<const float4*>(packed),
-                           density_factor, neighbor_opacities, density);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    launch_fwd<false>(N, K, 0, x, reinterpret_cast<const long long*>(nbr_idx), centers, inv_scaled_rot, strengths,
+                      reinterpret_cast<const float4*>(packed), nullptr, density_factor, TailArgs{}, neighbor_opacities, density, nullptr,
+                      nullptr, (hipStream_t)stream);
+    return sgr_launch_status();
+}
+
+int sgr_sdf_field_forward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
+                          const float* strengths, const float* min_scaling, float density_factor, float density_threshold,
+                          float opacity_min_clamp, float* neighbor_opacities, float* density, float* beta, float* sdf,
+                          const float* packed, void* stream)
+{
+    if (N <= 0) return 0;
+    if (K <= 0 || P <= 0 || !x || !nbr_idx || !centers || !inv_scaled_rot || !strengths || !min_scaling || !density || !beta || !sdf ||
+        !(density_threshold > 0.f) || misaligned16(packed))
+        return SGR_E_INVALID;
+    launch_fwd<true>(N, K, P, x, reinterpret_cast<const long long*>(nbr_idx), centers, inv_scaled_rot, strengths,
+                     reinterpret_cast<const float4*>(packed), min_scaling, density_factor, tail_args(density_threshold, opacity_min_clamp),
+                     neighbor_opacities, density, beta, sdf, (hipStream_t)stream);
+    return sgr_launch_status();
 }
 
 int sgr_density_field_backward(int N, int K, const float* x, const int64_t* nbr_idx, const float* centers,
@@ -817,7 +681,7 @@ int sgr_density_field_backward(int N, int K, const float* x, const int64_t* nbr_
     hipLaunchKernelGGL(k_density_bwd, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, K, x,
                        reinterpret_cast<const long long*>(nbr_idx), centers, inv_scaled_rot, strengths, reinterpret_cast<const float4*>(packed),
                        density_factor, dL_dopacities, dL_ddensity, dL_dx, dL_dcenters, dL_dinv_scaled_rot, dL_dstrengths);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_scaled_rotation_forward(int P, const float* quaternions, const float* scaling, int inverse_scales, float* out, void* stream)
@@ -826,7 +690,7 @@ int sgr_scaled_rotation_forward(int P, const float* quaternions, const float* sc
     if (!quaternions || !scaling || !out || ((uintptr_t)quaternions & 15)) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_scaled_rotation_fwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, quaternions, scaling,
                        inverse_scales, out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_scaled_rotation_backward(int P, const float* quaternions, const float* scaling, int inverse_scales, const float* dL_dout,
@@ -838,7 +702,7 @@ int sgr_scaled_rotation_backward(int P, const float* quaternions, const float* s
         return SGR_E_INVALID;
     hipLaunchKernelGGL(k_scaled_rotation_bwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, quaternions, scaling,
                        inverse_scales, dL_dout, dL_dquaternions, dL_dscaling);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_view_depth_rgb(int P, const float* centers, const float* viewmatrix, float* out, void* stream)
@@ -846,7 +710,7 @@ int sgr_view_depth_rgb(int P, const float* centers, const float* viewmatrix, flo
     if (P <= 0) return 0;
     if (!centers || !viewmatrix || !out) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_view_depth_rgb, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, centers, viewmatrix, out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_view_std(int P, const float* centers, const float* quaternions, const float* scaling, const float* cam_center, float* out,
@@ -856,7 +720,7 @@ int sgr_view_std(int P, const float* centers, const float* quaternions, const fl
     if (!centers || !quaternions || !scaling || !cam_center || !out || ((uintptr_t)quaternions & 15)) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_view_std, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, centers, quaternions, scaling, cam_center,
                        out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_unproject_pixels(int n, const int64_t* picked, const float* depth, int width, int height, float tanfovx, float tanfovy,
@@ -868,7 +732,7 @@ int sgr_unproject_pixels(int n, const int64_t* picked, const float* depth, int w
     const float f_ndc_x = ((float)width / (2.0f * tanfovx)) * 2.0f / (float)m, f_ndc_y = ((float)height / (2.0f * tanfovy)) * 2.0f / (float)m;
     hipLaunchKernelGGL(k_unproject_pixels, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, picked, depth, width, height,
                        f_ndc_x, f_ndc_y, viewmatrix, world);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_pack_gaussians(int P, const float* centers, const float* inv_scaled_rot, const float* strengths, float* packed, void* stream)
@@ -877,15 +741,12 @@ int sgr_pack_gaussians(int P, const float* centers, const float* inv_scaled_rot,
     if (!centers || !inv_scaled_rot || !strengths || !packed || ((uintptr_t)packed & 15)) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_pack_gaussians, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, centers, inv_scaled_rot,
                        strengths, reinterpret_cast<float4*>(packed));
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 size_t sgr_density_field_backward_scratch_bytes(int N, int K, int P)
 {
-    const size_t nk = (size_t)(N > 0 ? N : 0) * (size_t)(K > 0 ? K : 0), p = (size_t)(P > 0 ? P : 0);
-    const size_t blocks = (p + FSCAN_BLOCK - 1) / FSCAN_BLOCK + 1;
-    return sgr_align((p + 1) * 4) * 2 + sgr_align(blocks * 4) + 2 * sgr_align(nk * 4)   // cnt | start | block sums | rank | pair_list
-           + carve_group(nullptr, nk).total;                                            // | the radix grouping's buffers
+    return sgr_carve_ranked(nullptr, (size_t)(N > 0 ? N : 0) * (size_t)(K > 0 ? K : 0), P).total;
 }
 
 int sgr_density_field_backward_gather(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers,
@@ -899,93 +760,65 @@ int sgr_density_field_backward_gather(int N, int K, int P, const float* x, const
         !strengths || !dL_dcenters || !dL_dinv_scaled_rot || !dL_dstrengths || !scratch || (size_t)N * K > 0xFFFFFFFFull)
         return SGR_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const size_t nk = (size_t)N * K, pa = sgr_align(((size_t)P + 1) * 4);
-    const int n_blocks = (P + FSCAN_BLOCK - 1) / FSCAN_BLOCK;
-    const size_t ba = sgr_align(((size_t)n_blocks + 1) * 4);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(scratch);
-    uint32_t* start = reinterpret_cast<uint32_t*>(scratch + pa);
-    uint32_t* block_sums = reinterpret_cast<uint32_t*>(scratch + 2 * pa);
-    uint32_t* rank = reinterpret_cast<uint32_t*>(scratch + 2 * pa + ba);
-    uint32_t* pair_list = reinterpret_cast<uint32_t*>(scratch + 2 * pa + ba + sgr_align(nk * 4));
+    const size_t nk = (size_t)N * K;
+    const SgrRankedScratch sc = sgr_carve_ranked(scratch, nk, P);
     const long long* nbr = reinterpret_cast<const long long*>(nbr_idx);
-    const uint32_t* pairs = pair_list;
-    if (group_by_atomics() || N == 0) {
-        if (hipMemsetAsync(cnt, 0, ((size_t)P + 1) * 4, s) != hipSuccess) return SGR_E_HIP;
-        if (N > 0) {
-            hipLaunchKernelGGL(k_density_bwd_rank, dim3((N + 255) / 256), dim3(256), 0, s, N, K, x, nbr, centers, inv_scaled_rot,
-                               strengths, reinterpret_cast<const float4*>(packed), density_factor, dL_dopacities, dL_ddensity, dL_dx, cnt, rank);
-        }
-        hipLaunchKernelGGL(k_fscan_sums, dim3(n_blocks), dim3(256), 0, s, P, cnt, block_sums);
-        hipLaunchKernelGGL(k_fscan_top, dim3(1), dim3(1024), 0, s, n_blocks, block_sums, start + P);
-        hipLaunchKernelGGL(k_fscan_apply, dim3(n_blocks), dim3(256), 0, s, P, cnt, block_sums, start);
-        if (N > 0) {
-            hipLaunchKernelGGL(k_density_bwd_fill, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, (long long)nk, nbr, start, rank,
-                               pair_list);
-        }
+    const float4* pk = reinterpret_cast<const float4*>(packed);
+    const uint32_t* pairs = sc.list;
+    if (dL_dx && N > 0)
+        launch_dx<false>(N, K, 0, x, nbr, centers, inv_scaled_rot, strengths, pk, density_factor, dL_dopacities, dL_ddensity, dL_dx, s);
+    if (sgr_group_by_atomics() || N == 0) {
+        if (hipMemsetAsync(sc.cnt, 0, ((size_t)P + 1) * 4, s) != hipSuccess) return SGR_E_HIP;
+        if (N > 0) hipLaunchKernelGGL(k_density_bwd_rank, dim3(blocks256(nk)), dim3(256), 0, s, (long long)nk, nbr, sc.cnt, sc.rank);
+        sgr_launch_scan(P, sc.cnt, sc.block_sums, sc.start, s);
+        if (N > 0) hipLaunchKernelGGL(k_density_bwd_fill, dim3(blocks256(nk)), dim3(256), 0, s, (long long)nk, nbr, sc.start, sc.rank, sc.list);
     } else {
-        if (dL_dx && K == 16) {   // the gradient of the sample positions: a lane per pair
-            hipLaunchKernelGGL(k_density_dx16, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, (long long)nk, x, nbr, centers,
-                               inv_scaled_rot, strengths, reinterpret_cast<const float4*>(packed), density_factor, dL_dopacities,
-                               dL_ddensity, dL_dx);
-        } else if (dL_dx) {       // ... a lane per sample (no atomics in this mode)
-            hipLaunchKernelGGL(k_density_bwd_rank, dim3((N + 255) / 256), dim3(256), 0, s, N, K, x, nbr, centers, inv_scaled_rot,
-                               strengths, reinterpret_cast<const float4*>(packed), density_factor, dL_dopacities, dL_ddensity, dL_dx,
-                               (uint32_t*)nullptr, rank);
-        }
-        char* gscratch = scratch + 2 * pa + ba + 2 * sgr_align(nk * 4);
-        const int rc = launch_group_by_key((long long)nk, nbr, P, gscratch, start, &pairs, s);
+        const int rc = sgr_group_by_key((long long)nk, nbr, P, sc.group, sc.start, &pairs, s);
         if (rc < 0) return rc;
     }
-    hipLaunchKernelGGL(k_density_bwd_gather, dim3((unsigned)(((size_t)P * 16 + 255) / 256)), dim3(256), 0, s, P, K, x, centers, inv_scaled_rot, strengths,
-                       reinterpret_cast<const float4*>(packed), density_factor, dL_dopacities, dL_ddensity, start, pairs, dL_dcenters, dL_dinv_scaled_rot, dL_dstrengths);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    hipLaunchKernelGGL(k_density_bwd_gather<false>, dim3(blocks256((size_t)P * 16)), dim3(256), 0, s, P, K, x, centers, inv_scaled_rot,
+                       strengths, pk, density_factor, dL_dopacities, dL_ddensity, (const float*)nullptr, sc.start, pairs, dL_dcenters,
+                       dL_dinv_scaled_rot, dL_dstrengths, (float*)nullptr);
+    return sgr_launch_status();
 }
 
-size_t sgr_scatter_add_rows_scratch_bytes(long long N, int P)
+size_t sgr_sdf_field_backward_scratch_bytes(int N, int K, int P)
 {
-    const size_t n = (size_t)(N > 0 ? N : 0), p = (size_t)(P > 0 ? P : 0);
-    const size_t blocks = (p + FSCAN_BLOCK - 1) / FSCAN_BLOCK + 1;
-    return sgr_align((p + 1) * 4) * 2 + sgr_align(blocks * 4) + 2 * sgr_align(n * 4)   // cnt | start | block sums | rank | list
-           + carve_group(nullptr, n).total;                                           // | the radix grouping's buffers
+    const size_t n = (size_t)(N > 0 ? N : 0), nk = n * (size_t)(K > 0 ? K : 0), p = (size_t)(P > 0 ? P : 0);
+    return sgr_align((p + 1) * 4) + 2 * sgr_align(n * 4) + sgr_group_scratch_bytes(nk);   // start | gD | gB | the grouping's buffers
 }
 
-int sgr_scatter_add_rows(long long N, const int64_t* idx, const float* src, int W, int P, float* out, char* scratch, void* stream)
+int sgr_sdf_field_backward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
+                           const float* strengths, float density_factor, float density_threshold, float opacity_min_clamp,
+                           const float* density, const float* beta, const float* dL_dopacities, const float* dL_ddensity,
+                           const float* dL_dbeta, const float* dL_dsdf, float* dL_dx, float* dL_dcenters, float* dL_dinv_scaled_rot,
+                           float* dL_dstrengths, float* dL_dmin_scaling, char* scratch, const float* packed, void* stream)
 {
     if (P <= 0) return 0;
-    if (N < 0 || W < 1 || W > 4 || (N > 0 && (!idx || !src)) || !out || !scratch || (unsigned long long)N > 0xFFFFFFFFull)
+    if (N < 0 || K <= 0 || (N > 0 && (!x || !nbr_idx || !density || !beta)) || !centers || !inv_scaled_rot || !strengths || !dL_dcenters ||
+        !dL_dinv_scaled_rot || !dL_dstrengths || !dL_dmin_scaling || !scratch || !(density_threshold > 0.f) || misaligned16(packed) ||
+        (size_t)(N > 0 ? N : 0) * K > 0xFFFFFFFFull)
         return SGR_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    const size_t pa = sgr_align(((size_t)P + 1) * 4);
-    const int n_blocks = (P + FSCAN_BLOCK - 1) / FSCAN_BLOCK;
-    const size_t ba = sgr_align(((size_t)n_blocks + 1) * 4);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(scratch);
-    uint32_t* start = reinterpret_cast<uint32_t*>(scratch + pa);
-    uint32_t* block_sums = reinterpret_cast<uint32_t*>(scratch + 2 * pa);
-    uint32_t* rank = reinterpret_cast<uint32_t*>(scratch + 2 * pa + ba);
-    uint32_t* list = reinterpret_cast<uint32_t*>(scratch + 2 * pa + ba + sgr_align((size_t)N * 4));
-    const long long* ix = reinterpret_cast<const long long*>(idx);
-    const uint32_t* entries = list;
-    if (group_by_atomics() || N == 0) {
-        if (hipMemsetAsync(cnt, 0, ((size_t)P + 1) * 4, s) != hipSuccess) return SGR_E_HIP;
-        const unsigned nb = (unsigned)(((size_t)N + 255) / 256);
-        if (N > 0) hipLaunchKernelGGL(k_rows_rank, dim3(nb), dim3(256), 0, s, N, ix, P, cnt, rank);
-        hipLaunchKernelGGL(k_fscan_sums, dim3(n_blocks), dim3(256), 0, s, P, cnt, block_sums);
-        hipLaunchKernelGGL(k_fscan_top, dim3(1), dim3(1024), 0, s, n_blocks, block_sums, start + P);
-        hipLaunchKernelGGL(k_fscan_apply, dim3(n_blocks), dim3(256), 0, s, P, cnt, block_sums, start);
-        if (N > 0) hipLaunchKernelGGL(k_rows_fill, dim3(nb), dim3(256), 0, s, N, ix, P, start, rank, list);
-    } else {
-        char* gscratch = scratch + 2 * pa + ba + 2 * sgr_align((size_t)N * 4);
-        const int rc = launch_group_by_key(N, ix, P, gscratch, start, &entries, s);
-        if (rc < 0) return rc;
+    const TailArgs ta = tail_args(density_threshold, opacity_min_clamp);
+    const size_t nk = (size_t)N * K, pa = sgr_align(((size_t)P + 1) * 4), na = sgr_align((size_t)N * 4);
+    uint32_t* start = reinterpret_cast<uint32_t*>(scratch);
+    float* gD = reinterpret_cast<float*>(scratch + pa);
+    float* gB = reinterpret_cast<float*>(scratch + pa + na);
+    const long long* nbr = reinterpret_cast<const long long*>(nbr_idx);
+    const float4* pk = reinterpret_cast<const float4*>(packed);
+    const uint32_t* pairs = nullptr;
+    if (N > 0) {
+        hipLaunchKernelGGL(k_sdf_tail_bwd, dim3(blocks256((size_t)N)), dim3(256), 0, s, N, K, density, beta, dL_ddensity, dL_dbeta, dL_dsdf,
+                           ta, gD, gB);
+        if (dL_dx) launch_dx<true>(N, K, P, x, nbr, centers, inv_scaled_rot, strengths, pk, density_factor, dL_dopacities, gD, dL_dx, s);
     }
-    const unsigned gb = (unsigned)(((size_t)P * 16 + 255) / 256);
-    switch (W) {
-        case 1: hipLaunchKernelGGL(k_rows_gather<1>, dim3(gb), dim3(256), 0, s, P, src, start, entries, out); break;
-        case 2: hipLaunchKernelGGL(k_rows_gather<2>, dim3(gb), dim3(256), 0, s, P, src, start, entries, out); break;
-        case 3: hipLaunchKernelGGL(k_rows_gather<3>, dim3(gb), dim3(256), 0, s, P, src, start, entries, out); break;
-        default: hipLaunchKernelGGL(k_rows_gather<4>, dim3(gb), dim3(256), 0, s, P, src, start, entries, out); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    const int rc = sgr_group_by_key((long long)nk, nbr, P, scratch + pa + 2 * na, start, &pairs, s);
+    if (rc < 0) return rc;
+    hipLaunchKernelGGL(k_density_bwd_gather<true>, dim3(blocks256((size_t)P * 16)), dim3(256), 0, s, P, K, x, centers, inv_scaled_rot,
+                       strengths, pk, density_factor, dL_dopacities, gD, gB, start, pairs, dL_dcenters, dL_dinv_scaled_rot, dL_dstrengths,
+                       dL_dmin_scaling);
+    return sgr_launch_status();
 }
 
 int sgr_level_set_points(int N, int K, const float* world_points, const int64_t* nbr_idx, const float* cam_center,
@@ -1008,7 +841,7 @@ int sgr_level_set_points(int N, int K, const float* world_points, const int64_t*
         hipLaunchKernelGGL(k_level_set<LS_MAX_RANGE>, dim3((N + 127) / 128), dim3(128), 0, (hipStream_t)stream, N, K, world_points,
                            reinterpret_cast<const long long*>(nbr_idx), cam_center, centers, inv_scaled_rot, strengths, reinterpret_cast<const float4*>(packed), gaussian_std,
                            la, n_range, range_size, density_factor, valid, points, normals);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"

@@ -92,7 +92,7 @@ int sgr_dist2(int P, const float* points, float* meanDists, void* stream)
     if (!points || !meanDists) return SGR_E_INVALID;
     hipLaunchKernelGGL((k_knn<3, true>), dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, points, P, points,
                        (float*)nullptr, (int64_t*)nullptr, meanDists);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_knn(int N, const float* query, int M, const float* ref, int K, float* dists, int64_t* idx, void* stream)
@@ -110,7 +110,7 @@ int sgr_knn(int N, const float* query, int M, const float* ref, int K, float* di
         case 32: launch_knn<32>(N, query, M, ref, dists, idx, s); break;
         default: return SGR_E_INVALID;  // supported K: 1,2,3,4,8,16,32
     }
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"
@@ -1087,7 +1087,7 @@ int sgr_knn_grid(int N, const float* query, int M, const float* ref, int K, floa
         case 32: launch_grid_query<32>(self, N, query, M, ref, gs, G, dists, idx, s); break;
         default: return SGR_E_INVALID;
     }
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_dist2_grid(int P, const float* points, float* meanDists, char* scratch, void* stream)
@@ -1102,7 +1102,7 @@ int sgr_dist2_grid(int P, const float* points, float* meanDists, char* scratch, 
                        gs.cell_start, gs.sorted, (float*)nullptr, (int64_t*)nullptr, meanDists, &gs.hdr->far_count, gs.far_list,
                        gs.far_cap, grid_max_ring(), &gs.hdr->ball_count, gs.ball_list, gs.ball_u2);
     launch_far<3, true>(P, points, P, points, gs, G, nullptr, nullptr, meanDists, s);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"

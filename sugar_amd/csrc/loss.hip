@@ -360,7 +360,7 @@ int sgr_l1_ssim_forward_job(int channels, int width, int height, const float* im
     if (loss_out)  // (NULL: the caller asks sgr_l1_ssim_backward_ex for the value)
         hipLaunchKernelGGL(k_l1_ssim_finish, dim3(1), dim3(1024), 0, s, partial, n_tiles, (double)channels * width * height, lambda,
                            loss_out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_l1_ssim_backward(int channels, int width, int height, const float* img, const float* gt, float lambda,
@@ -385,7 +385,7 @@ int sgr_l1_ssim_backward_ex(int channels, int width, int height, const float* im
     const int n_partial = ((width + LT - 1) / LT) * ((height + LTY - 1) / LTY) * channels;
     hipLaunchKernelGGL(k_l1_ssim_bwd, dim3(8 * ((n_tiles + 7) / 8) + (loss_out ? 8 : 0)), dim3(256), 0, s, width, height, tiles_x, tiles_y,
                        n_tiles, img, gt, make_window(), dm1, ds1, ds12, grad_loss, lambda, inv_n, n, grad_img, partial, n_partial, loss_out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"

@@ -29,8 +29,6 @@
 #define MC_TABLE_QUAL static __device__ const
 #include "mc_table.h"
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define MC_TX 8

@@ -24,8 +24,6 @@
 
 #include <cmath>
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define MB_EPS_NORMALIZE 1e-12f   // torch.nn.functional.normalize

@@ -46,8 +46,6 @@
 #include "../../include/sugar_raster.h"
 #include "sgr_common.h"
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define MD_T 256

@@ -26,8 +26,6 @@
 #include "../../include/sugar_raster.h"
 #include "sgr_common.h"
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 __global__ void __launch_bounds__(256) k_peel_count(int E, int n_slots, const int32_t* __restrict__ offsets, const int32_t* __restrict__ items,

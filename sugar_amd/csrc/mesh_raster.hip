@@ -31,8 +31,6 @@
 
 #include <string>
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define MR_EPS 1e-8f          // kEpsilon, pytorch3d/csrc/utils/geometry_utils.cuh

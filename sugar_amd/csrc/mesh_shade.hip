@@ -16,8 +16,6 @@
 
 #include <cmath>
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define MS_EPS 1e-10f        // softmax_rgb_blend's eps

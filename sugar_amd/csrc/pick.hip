@@ -278,7 +278,7 @@ int sgr_pick_pixels(int n_pix, const float* depth, int k, uint32_t seed, int64_t
     hipLaunchKernelGGL(k_pick_scan, dim3(1), dim3(1024), 0, s, blocks, blk);
     hipLaunchKernelGGL(k_pick_write, dim3(blocks), dim3(PICK_BLOCK), 0, s, n_pix, depth, seed, st, blk, k, picked, count, n_valid);
     hipLaunchKernelGGL(k_pick_pad, dim3((k + 255) / 256), dim3(256), 0, s, k, st, picked);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_compact_level_rows(int N, int L, const uint8_t* valid, const uint32_t* n_rows, const float* points, const float* normals,
@@ -293,7 +293,7 @@ int sgr_compact_level_rows(int N, int L, const uint8_t* valid, const uint32_t* n
     hipLaunchKernelGGL(k_rows_count, dim3(nb, L), dim3(ROWS_BLOCK), 0, (hipStream_t)stream, N, valid, n_rows, blk);
     hipLaunchKernelGGL(k_rows_write, dim3(nb, L), dim3(ROWS_BLOCK), 0, (hipStream_t)stream, N, valid, n_rows, blk, points, normals, tag_a, tag_b,
                        rows_out, points_out, normals_out, tag_a_out, tag_b_out, counts);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"

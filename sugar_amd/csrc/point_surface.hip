@@ -35,8 +35,6 @@
 #include "../../include/sugar_raster.h"
 #include "sgr_common.h"
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define PS_BRICK 8

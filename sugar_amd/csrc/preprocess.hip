@@ -1308,7 +1308,7 @@ extern "C" int sgr_sh_to_rgb_forward(int P, int D, int M, const float* sh, const
     ShRgbArgs a;
     if (!colors || sh_rgb_args(a, P, D, M, sh, positions, camera_centers, n_centers, directions) < 0) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_sh_to_rgb_fwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, colors);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 extern "C" int sgr_sh_to_rgb_backward(int P, int D, int M, const float* sh, const float* positions, const float* camera_centers,
@@ -1320,5 +1320,5 @@ extern "C" int sgr_sh_to_rgb_backward(int P, int D, int M, const float* sh, cons
     if (!dL_dcolors || sh_rgb_args(a, P, D, M, sh, positions, camera_centers, n_centers, directions) < 0) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_sh_to_rgb_bwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, dL_dcolors, dL_dsh,
                        dL_dpositions, dL_ddirections);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }

@@ -1,5 +1,6 @@
 // sdf_regulariser.hip -- the tensor code of SuGaR's coarse-stage SDF regulariser (sugar_trainers/coarse_sdf.py:566-716) that runs
-// inside methods of the `SuGaR` class, as gfx950 kernels.  Four operations, each a forward and a backward:
+// inside methods of the `SuGaR` class, as gfx950 kernels.  Three operations, each a forward and a backward (the fourth, the SDF field,
+// is the SDF = true half of the density kernel family in csrc/field.hip):
 //
 //   sample transform : sugar_scene/sugar_model.py:924-926    x_n = mu_i + rot(q_i, f * s_i (.) eps_n),  i = idx[n]
 //                      rot(q, v) = vector part of q (x) (0, v) (x) conj(q), q NOT normalised (pytorch3d's quaternion_apply).
@@ -10,14 +11,6 @@
 //                      padding 'border', align_corners False.  The depth map is read through its strides.  Backward: the points through
 //                      the bilinear derivatives and the projection; the depth map by float atomic adds (as torch's own
 //                      grid_sampler_2d_backward: the one output here that is not bit-reproducible).
-//   sdf field        : :1247-1307 with beta_mode 'average': neighbour opacities and density exactly as csrc/field.hip forms them (same
-//                      expressions, same translation-unit flags), then
-//                        d' = density < 1 ? density : density / (density + 1e-12)      (the denominator carries no gradient)
-//                        beta = mean_k min_scaling[nbr_k]
-//                        sdf = beta * (sqrt(-2 ln max(d', opacity_min_clamp)) - sqrt(-2 ln min(threshold, 1)))
-//                      Backward: the (sample, neighbour) pairs are grouped by Gaussian once; one gather kernel writes the 13 sums of
-//                      field.hip's k_density_bwd_gather plus dmin_scaling.  The tail's derivative is evaluated in the reference's
-//                      operation order, so rows with density >= 1 carry what float32 autograd gives there (sqrt(0): non-finite).
 //
 // Every per-Gaussian gradient row is WRITTEN (zero where nothing references the Gaussian) and summed in a fixed order, without float
 // atomics: bit-identical from run to run.
@@ -39,18 +32,6 @@ __device__ __forceinline__ Q4 qmul(const Q4 a, const Q4 b)  // Hamilton product,
     return o;
 }
 __device__ __forceinline__ Q4 qconj(const Q4 a) { return Q4{a.w, -a.x, -a.y, -a.z}; }
-
-// sum over the 16 lanes of a DPP row, returned to every lane of the row (as in field.hip)
-__device__ __forceinline__ float row_sum16(float x)
-{
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x128, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x124, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x122, 0xF, 0xF, false));
-    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x121, 0xF, 0xF, false));
-    return x;
-}
-
-__device__ __forceinline__ long long wrap_row(long long i, int P) { return i < 0 ? i + P : i; }  // Python indexing, once
 
 // ---------------------------------------------------------------------------------------------------------- sample transform
 __global__ void __launch_bounds__(256) k_sample_fwd(long long N, int P, const long long* __restrict__ idx, const float* __restrict__ points,
@@ -109,14 +90,6 @@ __global__ void __launch_bounds__(256) k_sample_bwd_gather(int P, const float* _
 }
 
 // ------------------------------------------------------------------------------------------------------------- smallest axis
-// R = I + two_s * M (pytorch3d's quaternion_to_matrix, real part first)
-__device__ __forceinline__ void quat_M(float r, float i, float j, float k, float M[9])
-{
-    M[0] = -(j * j + k * k); M[1] = i * j - k * r;     M[2] = i * k + j * r;
-    M[3] = i * j + k * r;    M[4] = -(i * i + k * k);  M[5] = j * k - i * r;
-    M[6] = i * k - j * r;    M[7] = j * k + i * r;     M[8] = -(i * i + j * j);
-}
-
 __device__ __forceinline__ int smallest_of3(const float* __restrict__ s)  // the lowest index wins on ties
 {
     int j = 0;
@@ -260,264 +233,6 @@ __global__ void __launch_bounds__(256) k_depth_lookup_bwd(long long M, const flo
     }
 }
 
-// ----------------------------------------------------------------------------------------------------------------- sdf field
-// the neighbour record, its packed form and the warp w = B^T d exactly as csrc/field.hip has them
-struct GaussNbr {
-    float mx, my, mz;
-    float B[9];  // row-major 3x3
-    float s;
-};
-
-__device__ __forceinline__ GaussNbr load_nbr(long long g, const float* __restrict__ centers, const float* __restrict__ B,
-                                             const float* __restrict__ strengths, const float4* __restrict__ packed)
-{
-    GaussNbr n;
-    if (packed) {
-        const float4* r = packed + 4 * g;
-        const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-        n.mx = r0.x; n.my = r0.y; n.mz = r0.z; n.s = r0.w;
-        n.B[0] = r1.x; n.B[1] = r1.y; n.B[2] = r1.z; n.B[3] = r1.w;
-        n.B[4] = r2.x; n.B[5] = r2.y; n.B[6] = r2.z; n.B[7] = r2.w; n.B[8] = r3.x;
-        return n;
-    }
-    n.mx = centers[3 * g]; n.my = centers[3 * g + 1]; n.mz = centers[3 * g + 2];
-#pragma unroll
-    for (int i = 0; i < 9; i++) n.B[i] = B[9 * g + i];
-    n.s = strengths[g];
-    return n;
-}
-
-__device__ __forceinline__ void bt_mul(const float* Bm, float dx, float dy, float dz, float& w0, float& w1, float& w2)
-{
-    w0 = Bm[0] * dx + Bm[3] * dy + Bm[6] * dz;
-    w1 = Bm[1] * dx + Bm[4] * dy + Bm[7] * dz;
-    w2 = Bm[2] * dx + Bm[5] * dy + Bm[8] * dz;
-}
-
-struct TailArgs { float clamp_min, offset; };  // opacity_min_clamp; sqrt(-2 ln min(threshold, 1))
-
-__device__ __forceinline__ void sdf_tail(float density, float beta_sum, int K, const TailArgs ta, float& beta, float& sdf)
-{
-    const float dprime = density < 1.f ? density : density / (density + 1e-12f);
-    const float cl = fmaxf(dprime, ta.clamp_min);
-    beta = beta_sum / (float)K;
-    sdf = beta * (sqrtf(-2.f * logf(cl)) - ta.offset);
-}
-
-// K == 16: a lane per (sample, neighbour) pair, the sixteen pairs of a sample in one DPP row (as k_density_fwd16)
-__global__ void __launch_bounds__(256) k_sdf_fwd16(long long NK, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
-                                                   const float* __restrict__ centers, const float* __restrict__ B,
-                                                   const float* __restrict__ strengths, const float4* __restrict__ packed,
-                                                   const float* __restrict__ min_scaling, float factor, TailArgs ta,
-                                                   float* __restrict__ opac, float* __restrict__ density, float* __restrict__ beta,
-                                                   float* __restrict__ sdf)
-{
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= NK) return;   // (NK is a multiple of 16: rows leave whole)
-    const size_t n = (size_t)(p >> 4);
-    const long long gi = wrap_row(nbr[p], P);
-    float o = 0.f, ms = 0.f;
-    if (gi >= 0 && gi < P) {
-        const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
-        float w0, w1, w2;
-        bt_mul(g.B, x[3 * n] - g.mx, x[3 * n + 1] - g.my, x[3 * n + 2] - g.mz, w0, w1, w2);
-        const float q = fminf(fmaxf(w0 * w0 + w1 * w1 + w2 * w2, 0.f), 1e8f);
-        o = factor * g.s * __expf(-0.5f * q);
-        ms = min_scaling[gi];
-    }
-    if (opac) opac[p] = o;
-    const float sum = row_sum16(o), bsum = row_sum16(ms);
-    if ((threadIdx.x & 15) == 0) {
-        float b, s;
-        sdf_tail(sum, bsum, 16, ta, b, s);
-        density[n] = sum; beta[n] = b; sdf[n] = s;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_sdf_fwd(int N, int K, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
-                                                 const float* __restrict__ centers, const float* __restrict__ B,
-                                                 const float* __restrict__ strengths, const float4* __restrict__ packed,
-                                                 const float* __restrict__ min_scaling, float factor, TailArgs ta,
-                                                 float* __restrict__ opac, float* __restrict__ density, float* __restrict__ beta,
-                                                 float* __restrict__ sdf)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float px = x[3 * (size_t)n], py = x[3 * (size_t)n + 1], pz = x[3 * (size_t)n + 2];
-    float sum = 0.f, bsum = 0.f;
-    for (int k = 0; k < K; k++) {
-        const long long gi = wrap_row(nbr[(size_t)n * K + k], P);
-        float o = 0.f;
-        if (gi >= 0 && gi < P) {
-            const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
-            float w0, w1, w2;
-            bt_mul(g.B, px - g.mx, py - g.my, pz - g.mz, w0, w1, w2);
-            const float q = fminf(fmaxf(w0 * w0 + w1 * w1 + w2 * w2, 0.f), 1e8f);
-            o = factor * g.s * __expf(-0.5f * q);
-            bsum += min_scaling[gi];
-        }
-        if (opac) opac[(size_t)n * K + k] = o;
-        sum += o;
-    }
-    float b, s;
-    sdf_tail(sum, bsum, K, ta, b, s);
-    density[n] = sum; beta[n] = b; sdf[n] = s;
-}
-
-// per sample: the gradient that reaches the density (its own plus the sdf's, through the tail in the reference's operation order:
-// mul, sqrt, mul by -2, log, clamp, the division of the rows >= 1) and the gradient per neighbour of min_scaling (beta's / K)
-__global__ void __launch_bounds__(256) k_sdf_tail_bwd(int N, int K, const float* __restrict__ density, const float* __restrict__ beta,
-                                                      const float* __restrict__ g_den, const float* __restrict__ g_beta,
-                                                      const float* __restrict__ g_sdf, TailArgs ta, float* __restrict__ gD,
-                                                      float* __restrict__ gB)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float D = density[n];
-    const bool over = !(D < 1.f);
-    const float dprime = over ? D / (D + 1e-12f) : D;
-    const float cl = fmaxf(dprime, ta.clamp_min);
-    const float r = sqrtf(-2.f * logf(cl));
-    float gd = g_den ? g_den[n] : 0.f, gb = g_beta ? g_beta[n] : 0.f;
-    if (g_sdf) {
-        const float gs = g_sdf[n];
-        gb += gs * (r - ta.offset);
-        const float gr = gs * beta[n];
-        const float gL = gr / (2.f * r);
-        float gcl = (gL * -2.f) / cl;
-        if (!(dprime >= ta.clamp_min)) gcl = 0.f;      // clamp(min): the gradient passes where the input is >= min
-        gd += over ? gcl / (D + 1e-12f) : gcl;
-    }
-    gD[n] = gd;
-    gB[n] = gb / (float)K;
-}
-
-// the gradient of the sample positions, a lane per pair (K == 16) or per sample: k_density_dx16 / k_density_bwd_rank of field.hip
-__global__ void __launch_bounds__(256) k_sdf_dx16(long long NK, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
-                                                  const float* __restrict__ centers, const float* __restrict__ B,
-                                                  const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
-                                                  const float* __restrict__ g_opac, const float* __restrict__ gD, float* __restrict__ dx_out)
-{
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= NK) return;
-    const size_t n = (size_t)(p >> 4);
-    const long long gi = wrap_row(nbr[p], P);
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    if (gi >= 0 && gi < P) {
-        const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
-        float w0, w1, w2;
-        bt_mul(g.B, x[3 * n] - g.mx, x[3 * n + 1] - g.my, x[3 * n + 2] - g.mz, w0, w1, w2);
-        const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
-        const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-        const float go = (g_opac ? g_opac[p] : 0.f) + gD[n];
-        const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
-        const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
-        ax = g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
-        ay = g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
-        az = g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
-    }
-    ax = row_sum16(ax); ay = row_sum16(ay); az = row_sum16(az);
-    if ((threadIdx.x & 15) == 0) { dx_out[3 * n] = ax; dx_out[3 * n + 1] = ay; dx_out[3 * n + 2] = az; }
-}
-
-__global__ void __launch_bounds__(256) k_sdf_dx(int N, int K, int P, const float* __restrict__ x, const long long* __restrict__ nbr,
-                                                const float* __restrict__ centers, const float* __restrict__ B,
-                                                const float* __restrict__ strengths, const float4* __restrict__ packed, float factor,
-                                                const float* __restrict__ g_opac, const float* __restrict__ gD, float* __restrict__ dx_out)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float px = x[3 * (size_t)n], py = x[3 * (size_t)n + 1], pz = x[3 * (size_t)n + 2];
-    const float gd = gD[n];
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int k = 0; k < K; k++) {
-        const size_t p = (size_t)n * K + k;
-        const long long gi = wrap_row(nbr[p], P);
-        if (gi < 0 || gi >= P) continue;
-        const GaussNbr g = load_nbr(gi, centers, B, strengths, packed);
-        float w0, w1, w2;
-        bt_mul(g.B, px - g.mx, py - g.my, pz - g.mz, w0, w1, w2);
-        const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
-        const float e = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-        const float go = (g_opac ? g_opac[p] : 0.f) + gd;
-        const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * e * go : 0.f;
-        const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
-        ax += g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
-        ay += g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
-        az += g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
-    }
-    dx_out[3 * (size_t)n] = ax; dx_out[3 * (size_t)n + 1] = ay; dx_out[3 * (size_t)n + 2] = az;
-}
-
-// sixteen lanes per Gaussian over its grouped pairs: the 13 sums of k_density_bwd_gather and dmin_scaling as the fourteenth
-__global__ void __launch_bounds__(256) k_sdf_bwd_gather(int P, int K, const float* __restrict__ x, const float* __restrict__ centers,
-                                                        const float* __restrict__ B, const float* __restrict__ strengths,
-                                                        const float4* __restrict__ packed, float factor, const float* __restrict__ g_opac,
-                                                        const float* __restrict__ gD, const float* __restrict__ gB,
-                                                        const uint32_t* __restrict__ start, const uint32_t* __restrict__ pair_list,
-                                                        float* __restrict__ dcenters, float* __restrict__ dB,
-                                                        float* __restrict__ dstrengths, float* __restrict__ dmin_scaling)
-{
-    const int t = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) >> 4);
-    const uint32_t sub = threadIdx.x & 15;
-    if (t >= P) return;
-    const GaussNbr g = load_nbr(t, centers, B, strengths, packed);
-    float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, ds = 0.f, dm = 0.f;
-    float b[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) b[i] = 0.f;
-    const uint32_t e0 = start[t], e1 = start[t + 1];
-    for (uint32_t e = e0 + sub; e < e1; e += 16) {
-        const uint32_t p = pair_list[e];
-        const uint32_t n = p / (uint32_t)K;
-        const float dx = x[3 * (size_t)n] - g.mx, dy = x[3 * (size_t)n + 1] - g.my, dz = x[3 * (size_t)n + 2] - g.mz;
-        float w0, w1, w2;
-        bt_mul(g.B, dx, dy, dz, w0, w1, w2);
-        const float q_raw = w0 * w0 + w1 * w1 + w2 * w2;
-        const float ex = __expf(-0.5f * fminf(fmaxf(q_raw, 0.f), 1e8f));
-        const float go = (g_opac ? g_opac[p] : 0.f) + gD[n];
-        ds += go * factor * ex;
-        dm += gB[n];
-        const float dq = (q_raw > 0.f && q_raw < 1e8f) ? -0.5f * factor * g.s * ex * go : 0.f;
-        const float dw0 = 2.f * w0 * dq, dw1 = 2.f * w1 * dq, dw2 = 2.f * w2 * dq;
-        dc0 -= g.B[0] * dw0 + g.B[1] * dw1 + g.B[2] * dw2;
-        dc1 -= g.B[3] * dw0 + g.B[4] * dw1 + g.B[5] * dw2;
-        dc2 -= g.B[6] * dw0 + g.B[7] * dw1 + g.B[8] * dw2;
-        b[0] += dx * dw0; b[1] += dx * dw1; b[2] += dx * dw2;
-        b[3] += dy * dw0; b[4] += dy * dw1; b[5] += dy * dw2;
-        b[6] += dz * dw0; b[7] += dz * dw1; b[8] += dz * dw2;
-    }
-    dc0 = row_sum16(dc0); dc1 = row_sum16(dc1); dc2 = row_sum16(dc2); ds = row_sum16(ds); dm = row_sum16(dm);
-#pragma unroll
-    for (int i = 0; i < 9; i++) b[i] = row_sum16(b[i]);
-    if (sub == 0) {
-        dcenters[3 * (size_t)t] = dc0; dcenters[3 * (size_t)t + 1] = dc1; dcenters[3 * (size_t)t + 2] = dc2;
-        dstrengths[t] = ds;
-        dmin_scaling[t] = dm;
-    }
-    if (sub < 9) {
-        float v = b[0];
-#pragma unroll
-        for (int i = 1; i < 9; i++) v = (sub == (uint32_t)i) ? b[i] : v;
-        dB[9 * (size_t)t + sub] = v;
-    }
-}
-
-TailArgs tail_args(float density_threshold, float opacity_min_clamp)
-{
-    const double th = density_threshold < 1.f ? (double)density_threshold : 1.0;
-    return TailArgs{opacity_min_clamp, (float)sqrt(-2.0 * log(th))};   // (np.sqrt(-2 np.log(min(threshold, 1))), then float32)
-}
-
-inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-// start[0..P] of the grouping when there is nothing to group
-int zero_start(uint32_t* start, int P, hipStream_t s)
-{
-    return hipMemsetAsync(start, 0, ((size_t)P + 1) * 4, s) == hipSuccess ? 0 : SGR_E_HIP;
-}
-
 }  // namespace
 
 extern "C" {
@@ -531,7 +246,7 @@ int sgr_sample_transform_forward(long long N, int P, const int64_t* idx, const f
         return SGR_E_INVALID;
     hipLaunchKernelGGL(k_sample_fwd, dim3(blocks256((size_t)N)), dim3(256), 0, (hipStream_t)stream, N, P,
                        reinterpret_cast<const long long*>(idx), points, quaternions, scaling, noise, factor, out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 size_t sgr_sample_transform_backward_scratch_bytes(long long N, int P)
@@ -551,12 +266,11 @@ int sgr_sample_transform_backward(long long N, int P, const int64_t* idx, const 
     hipStream_t s = (hipStream_t)stream;
     uint32_t* start = reinterpret_cast<uint32_t*>(scratch);
     const uint32_t* list = nullptr;
-    int rc = N > 0 ? sgr_group_by_key(N, reinterpret_cast<const long long*>(idx), P, scratch + sgr_align(((size_t)P + 1) * 4), start, &list, s)
-                   : zero_start(start, P, s);
+    const int rc = sgr_group_by_key(N, reinterpret_cast<const long long*>(idx), P, scratch + sgr_align(((size_t)P + 1) * 4), start, &list, s);
     if (rc < 0) return rc;
     hipLaunchKernelGGL(k_sample_bwd_gather, dim3(blocks256((size_t)P * 16)), dim3(256), 0, s, P, quaternions, scaling, noise, dL_dout,
                        factor, start, list, dL_dpoints, dL_dquaternions, dL_dscaling);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_smallest_axis_forward(int P, const float* quaternions, const float* scaling, float* axis, int64_t* axis_idx, void* stream)
@@ -565,7 +279,7 @@ int sgr_smallest_axis_forward(int P, const float* quaternions, const float* scal
     if (!quaternions || !scaling || !axis || misaligned16(quaternions)) return SGR_E_INVALID;
     hipLaunchKernelGGL(k_smallest_axis_fwd, dim3(blocks256((size_t)P)), dim3(256), 0, (hipStream_t)stream, P, quaternions, scaling, axis,
                        reinterpret_cast<long long*>(axis_idx));
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_smallest_axis_backward(int P, const float* quaternions, const float* scaling, const float* dL_daxis, float* dL_dquaternions,
@@ -576,7 +290,7 @@ int sgr_smallest_axis_backward(int P, const float* quaternions, const float* sca
         return SGR_E_INVALID;
     hipLaunchKernelGGL(k_smallest_axis_bwd, dim3(blocks256((size_t)P)), dim3(256), 0, (hipStream_t)stream, P, quaternions, scaling,
                        dL_daxis, dL_dquaternions);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_depth_lookup_forward(long long M, const float* points_cam, const float* projection, const float* depth, long long stride_y,
@@ -588,7 +302,7 @@ int sgr_depth_lookup_forward(long long M, const float* points_cam, const float* 
         return SGR_E_INVALID;
     hipLaunchKernelGGL(k_depth_lookup_fwd, dim3(blocks256((size_t)M)), dim3(256), 0, (hipStream_t)stream, M, points_cam, projection, depth,
                        stride_y, stride_x, height, width, out);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 int sgr_depth_lookup_backward(long long M, const float* points_cam, const float* projection, const float* depth, long long stride_y,
@@ -603,77 +317,7 @@ int sgr_depth_lookup_backward(long long M, const float* points_cam, const float*
         return SGR_E_INVALID;
     hipLaunchKernelGGL(k_depth_lookup_bwd, dim3(blocks256((size_t)M)), dim3(256), 0, s, M, points_cam, projection, depth, stride_y,
                        stride_x, height, width, dL_dout, dL_dpoints_cam, dL_ddepth);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
-}
-
-int sgr_sdf_field_forward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
-                          const float* strengths, const float* min_scaling, float density_factor, float density_threshold,
-                          float opacity_min_clamp, float* neighbor_opacities, float* density, float* beta, float* sdf,
-                          const float* packed, void* stream)
-{
-    if (N <= 0) return 0;
-    if (K <= 0 || P <= 0 || !x || !nbr_idx || !centers || !inv_scaled_rot || !strengths || !min_scaling || !density || !beta || !sdf ||
-        !(density_threshold > 0.f) || misaligned16(packed))
-        return SGR_E_INVALID;
-    const TailArgs ta = tail_args(density_threshold, opacity_min_clamp);
-    const long long* nbr = reinterpret_cast<const long long*>(nbr_idx);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
-    if (K == 16) {
-        const long long nk = (long long)N * 16;
-        hipLaunchKernelGGL(k_sdf_fwd16, dim3(blocks256((size_t)nk)), dim3(256), 0, (hipStream_t)stream, nk, P, x, nbr, centers,
-                           inv_scaled_rot, strengths, pk, min_scaling, density_factor, ta, neighbor_opacities, density, beta, sdf);
-    } else {
-        hipLaunchKernelGGL(k_sdf_fwd, dim3(blocks256((size_t)N)), dim3(256), 0, (hipStream_t)stream, N, K, P, x, nbr, centers,
-                           inv_scaled_rot, strengths, pk, min_scaling, density_factor, ta, neighbor_opacities, density, beta, sdf);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
-}
-
-size_t sgr_sdf_field_backward_scratch_bytes(int N, int K, int P)
-{
-    const size_t n = (size_t)(N > 0 ? N : 0), nk = n * (size_t)(K > 0 ? K : 0), p = (size_t)(P > 0 ? P : 0);
-    return sgr_align((p + 1) * 4) + 2 * sgr_align(n * 4) + sgr_group_scratch_bytes(nk);   // start | gD | gB | the grouping's buffers
-}
-
-int sgr_sdf_field_backward(int N, int K, int P, const float* x, const int64_t* nbr_idx, const float* centers, const float* inv_scaled_rot,
-                           const float* strengths, float density_factor, float density_threshold, float opacity_min_clamp,
-                           const float* density, const float* beta, const float* dL_dopacities, const float* dL_ddensity,
-                           const float* dL_dbeta, const float* dL_dsdf, float* dL_dx, float* dL_dcenters, float* dL_dinv_scaled_rot,
-                           float* dL_dstrengths, float* dL_dmin_scaling, char* scratch, const float* packed, void* stream)
-{
-    if (P <= 0) return 0;
-    if (N < 0 || K <= 0 || (N > 0 && (!x || !nbr_idx || !density || !beta)) || !centers || !inv_scaled_rot || !strengths || !dL_dcenters ||
-        !dL_dinv_scaled_rot || !dL_dstrengths || !dL_dmin_scaling || !scratch || !(density_threshold > 0.f) || misaligned16(packed) ||
-        (size_t)(N > 0 ? N : 0) * K > 0xFFFFFFFFull)
-        return SGR_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    const TailArgs ta = tail_args(density_threshold, opacity_min_clamp);
-    const size_t nk = (size_t)N * K, pa = sgr_align(((size_t)P + 1) * 4), na = sgr_align((size_t)N * 4);
-    uint32_t* start = reinterpret_cast<uint32_t*>(scratch);
-    float* gD = reinterpret_cast<float*>(scratch + pa);
-    float* gB = reinterpret_cast<float*>(scratch + pa + na);
-    const long long* nbr = reinterpret_cast<const long long*>(nbr_idx);
-    const float4* pk = reinterpret_cast<const float4*>(packed);
-    const uint32_t* pairs = nullptr;
-    if (N > 0) {
-        hipLaunchKernelGGL(k_sdf_tail_bwd, dim3(blocks256((size_t)N)), dim3(256), 0, s, N, K, density, beta, dL_ddensity, dL_dbeta, dL_dsdf,
-                           ta, gD, gB);
-        if (dL_dx && K == 16)
-            hipLaunchKernelGGL(k_sdf_dx16, dim3(blocks256(nk)), dim3(256), 0, s, (long long)nk, P, x, nbr, centers, inv_scaled_rot,
-                               strengths, pk, density_factor, dL_dopacities, gD, dL_dx);
-        else if (dL_dx)
-            hipLaunchKernelGGL(k_sdf_dx, dim3(blocks256((size_t)N)), dim3(256), 0, s, N, K, P, x, nbr, centers, inv_scaled_rot, strengths,
-                               pk, density_factor, dL_dopacities, gD, dL_dx);
-        const int rc = sgr_group_by_key((long long)nk, nbr, P, scratch + pa + 2 * na, start, &pairs, s);
-        if (rc < 0) return rc;
-    } else {
-        const int rc = zero_start(start, P, s);
-        if (rc < 0) return rc;
-    }
-    hipLaunchKernelGGL(k_sdf_bwd_gather, dim3(blocks256((size_t)P * 16)), dim3(256), 0, s, P, K, x, centers, inv_scaled_rot, strengths, pk,
-                       density_factor, dL_dopacities, gD, gB, start, pairs, dL_dcenters, dL_dinv_scaled_rot, dL_dstrengths,
-                       dL_dmin_scaling);
-    return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP;
+    return sgr_launch_status();
 }
 
 }  // extern "C"

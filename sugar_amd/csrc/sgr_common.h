@@ -31,6 +31,10 @@ struct GeomRec {
 };
 static_assert(sizeof(GeomRec) == 48, "GeomRec must be 48 bytes");
 
+int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
+// what an entry point returns after its launches: 0, or SGR_E_HIP when one of them was refused
+static inline int sgr_launch_status() { return hipGetLastError() == hipSuccess ? 0 : SGR_E_HIP; }
+
 static inline size_t sgr_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline size_t sgr_geom_acc_offset(int P) { return sgr_align((size_t)(P > 0 ? P : 1) * 48); }
 size_t sgr_sort_scratch_bytes(int P);  // binning.hip

@@ -1,5 +1,6 @@
 // sgr_device.h -- device helpers shared by the translation units: the tile rectangle of preprocess.hip and binning.hip, and the
-// wave and workgroup prefix sums of every kernel that forms one (binning, k-NN grid, field scatter, pixel pick, marching cubes).
+// wave and workgroup prefix sums of every kernel that forms one (binning, k-NN grid, field scatter, pixel pick, marching cubes),
+// and the DPP row sum, quaternion matrix and index wrap of the field, regulariser and grouping kernels.
 #pragma once
 #include "sgr_common.h"
 
@@ -35,6 +36,31 @@ __device__ __forceinline__ uint32_t sgr_block_scan(uint32_t x, uint32_t* s_wave,
     __syncthreads();
     return total;
 }
+
+// ---- shared by field.hip, sdf_regulariser.hip and group.hip ---------------------------------------------------------
+// sum over the 16 lanes of a DPP row, returned to every lane of the row (row_ror:8 / 4 / 2 / 1 fold into the adds)
+__device__ __forceinline__ float row_sum16(float x)
+{
+    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x128, 0xF, 0xF, false));
+    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x124, 0xF, 0xF, false));
+    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x122, 0xF, 0xF, false));
+    x += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x121, 0xF, 0xF, false));
+    return x;
+}
+
+// R = I + two_s * M, two_s = 2 / |q|^2 (pytorch3d's quaternion_to_matrix, real part first)
+__device__ __forceinline__ void quat_M(float r, float i, float j, float k, float M[9])
+{
+    M[0] = -(j * j + k * k); M[1] = i * j - k * r;     M[2] = i * k + j * r;
+    M[3] = i * j + k * r;    M[4] = -(i * i + k * k);  M[5] = j * k - i * r;
+    M[6] = i * k - j * r;    M[7] = j * k + i * r;     M[8] = -(i * i + j * j);
+}
+
+// a row index as Python reads it: negative values wrap once (the caller checks 0 <= result < P)
+__device__ __forceinline__ long long wrap_row(long long i, int P) { return i < 0 ? i + P : i; }
+
+static inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+static inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
 
 __device__ __forceinline__ int sgr_f2i_sat(float v)
 {

@@ -27,8 +27,6 @@
 #include "../../include/sugar_raster.h"
 #include "sgr_device.h"
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define SS_BRICK 8

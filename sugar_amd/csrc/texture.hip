@@ -23,8 +23,6 @@
 
 #include <cmath>
 
-int sgr_fail(int code, const char* msg);  // capi.hip: sets sgr_last_error() of the calling thread
-
 namespace {
 
 #define TX_SH_C0 0.28209479177387814f   // SH2RGB, sugar_utils/spherical_harmonics.py

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # c per output and the kernels that write it; in brackets the largest measured max |HIP - ref64| / (2^-24 m) over every case
 C_OPAC = 8        # k_density_fwd16 / k_density_fwd, neighbor_opacities  [6.44]
 C_DENS = 8        # k_density_fwd16 (DPP row sum) / k_density_fwd (sequential), densities  [3.77]
-C_DX = 8          # k_density_dx16 / k_density_bwd_rank / k_density_bwd, dL/dx  [3.03]
+C_DX = 8          # k_density_dx16 / k_density_dx / k_density_bwd, dL/dx  [3.03]
 C_GAUSS = 16      # k_density_bwd_gather (or k_density_bwd's float atomics): dL/dcentres, dL/dB, dL/dstrengths  [5.15]
 C_HOT = 16        # the same for the Gaussian in every list (~N pairs: sixteen strided sums of N / 16 terms)  [0.39]
 C_ROWS = 8        # k_rows_gather (sgr_scatter_add_rows)  [2.19]
@@ -164,7 +164,7 @@ DENSITY_CASES = {
 @pytest.mark.parametrize("case", list(DENSITY_CASES))
 def test_density_field_forward_backward(case):
     """Every dispatch of the density field against the float64 restatement, per element.  K == 16 runs k_density_fwd16 and
-    k_density_dx16, any other K k_density_fwd and k_density_bwd_rank; the per-Gaussian gradients come from k_density_bwd_gather
+    k_density_dx16, any other K k_density_fwd and k_density_dx; the per-Gaussian gradients come from k_density_bwd_gather
     after the radix grouping (2 passes for P < 65536, 3 for the trainer cases; 16M+ pairs run k_fscan_top with per = 2), or
     with _DensityField.use_gather = False from the float atomics of k_density_bwd.  Every case but K = 1 has a Gaussian in every
     list; all have unreferenced Gaussians (rows exactly 0), repeated neighbours, q = 0, q > 1e8 (exactly 0) and strength 0."""
@@ -243,6 +243,49 @@ def test_density_field_c_abi_optional_pointers(K):
     assert _rel(a[1], r["densities"]) < 1e-5
 
 
+@pytest.mark.parametrize("K", [16, 8])
+@pytest.mark.parametrize("N", [1, 257])
+def test_sdf_field_carries_the_density_fields_bits(N, K):
+    """sdf_field and density_field run the two instances of one kernel family (csrc/field.hip, template <bool SDF>).  Asserted, bit
+    for bit: the neighbour opacities and the density of the two (the contract the SDF field documents), and -- with no gradient for
+    beta and sdf -- dcenters and dB of the backward; dmin_scaling is exactly 0 and so is every gradient row of an unreferenced
+    Gaussian.  P = 300 with 60 Gaussians that no sample references, a neighbour twice in row 0, factor 1.3, threshold 1.
+
+    While the SDF forward kept its pair arithmetic under the range check's branch the forward equalities did NOT hold (MI355X; also
+    with the separate k_sdf_* kernels before the family): the compiler paired the products of w = B^T d and |w|^2 into packed FP32
+    instructions there (one product rounded on its own) and left the density kernels scalar FMA chains; opacities differed by up to
+    8.94e-08, densities by 1.19e-07 at these shapes.  The SDF forward now runs the arithmetic for every lane and discards the
+    out-of-range ones.  Backward outputs that were not bit-equal before the family either, and are printed, not asserted: dx
+    (N = 257, K = 16: max |diff| 1.91e-06; equal in the other three cases) and dstrengths (N = 257, K = 16: 1.49e-08; equal in the
+    other three)."""
+    from sugar_amd.sdf_regulariser import sdf_field
+    P, used, factor = 300, 240, 1.3
+    g = torch.Generator().manual_seed(1000 * N + K)
+    ce = torch.rand(P, 3, generator=g, dtype=torch.float64) * 0.3
+    B = _rot(P, g) * (1.0 / (0.03 * torch.exp(0.4 * torch.randn(P, 3, generator=g, dtype=torch.float64))))[:, None]
+    st = torch.rand(P, 1, generator=g, dtype=torch.float64)
+    ms = 0.01 + 0.02 * torch.rand(P, generator=g)
+    nb = torch.randint(0, used, (N, K), generator=g)
+    nb[0, 1] = nb[0, 0]
+    x = ce[nb[:, 0]] + 0.03 * torch.randn(N, 3, generator=g, dtype=torch.float64)
+    go, gd = _grads_in(N, K, 77)
+    want = _run_density(x, nb, ce, B, st, factor, go, gd)
+
+    leaves = [t.float().to(DEV).requires_grad_(True) for t in (x, ce, B, st, ms)]
+    o, d, beta, sdf = sdf_field(leaves[0], nb.to(DEV), *leaves[1:], factor, 1.0, 1e-16)
+    ((o * go.float().to(DEV)).sum() + (d * gd.float().to(DEV)).sum()).backward()
+    got = dict(opacities=o.detach(), densities=d.detach(), dx=leaves[0].grad, dcenters=leaves[1].grad, dB=leaves[2].grad,
+               dstrengths=leaves[3].grad[:, 0])
+    assert float(want["opacities"].abs().max()) > 0 and float(want["dB"].abs().max()) > 0
+    for k, w in want.items():
+        print("EQUAL", N, K, k, bool(torch.equal(got[k], w)), f"max |diff| = {float((got[k] - w).abs().max()):.3g}")
+    assert float(leaves[4].grad.abs().max()) == 0.0
+    for k in ("dcenters", "dB", "dstrengths"):
+        assert float(got[k][used:].abs().max()) == 0.0, k
+    for k in ("dcenters", "dB", "opacities", "densities"):
+        assert torch.equal(got[k], want[k]), k
+
+
 ATOMICS_CASE = dict(P=2_500_000, N=200_003, K=16, factor=1.3, seed=31)   # P > 2^21: the P-scan's k_fscan_top runs with per = 2
 ATOMICS_ROWS = dict(M=3_000_001, W=3, P=2_500_000, seed=32)
 
@@ -269,7 +312,7 @@ def _rows_ref(idx, src, P):
 
 def _atomics_child(path):
     """run in a fresh process with SGR_GROUP_ATOMICS=1 (read once per process): the density backward and the row scatter grouped by
-    returning integer atomics (k_density_bwd_rank's ranks, k_density_bwd_fill, k_rows_rank, k_rows_fill)"""
+    returning integer atomics (k_density_bwd_rank, k_density_bwd_fill, k_rows_rank, k_rows_fill)"""
     from sugar_amd.row_gather import row_gather
     c = ATOMICS_CASE
     x, nb, ce, B, st, _ = _field_case(c["P"], c["N"], c["K"], c["seed"])

@@ -16,7 +16,7 @@ SIZES = [1, 63, 64, 65, 255, 256, 257, 2049, 4097]
 
 
 def _scatter_rows(n):
-    """the k_fscan_* chain: sgr_scatter_add_rows groups n entries by row with a radix sort whose digit offsets are that scan"""
+    """the k_fscan_* chain of csrc/group.hip: sgr_scatter_add_rows groups n entries by row with a radix sort whose digit offsets are that scan"""
     g = torch.Generator().manual_seed(n)
     P = n                                                       # the row count crosses the same boundaries
     ix = torch.randint(0, P, (n,), generator=g).to(DEV)
