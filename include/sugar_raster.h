@@ -615,6 +615,70 @@ int sgr_sdf_field_backward(int N, int K, int P, const float* x, const int64_t* n
                            const float* dL_dbeta, const float* dL_dsdf, float* dL_dx, float* dL_dcenters, float* dL_dinv_scaled_rot,
                            float* dL_dstrengths, float* dL_dmin_scaling, char* scratch, const float* packed, void* stream);
 
+/* ---- the coarse trainers' inline loss terms of the SDF regulariser (csrc/coarse_loss.hip; added under ABI version 4, additive) ----------
+ * The statements that sugar_trainers/coarse_sdf.py:606-716 (and coarse_density.py:610-730) write between the method calls above.  The
+ * conventions of the previous section hold: float32 contiguous tensors, int64 indices that wrap once (a sample or neighbour whose index
+ * is outside [-P, P) contributes nothing and is never dereferenced), unit quaternions real part first and 16-byte aligned, no host
+ * synchronisation.  world_to_view[16] and projection[16] are pytorch3d's row-vector matrices ([x y z 1] * M, row-major) and znear[1] the
+ * camera's near plane, all three read on the DEVICE; the depth map is read as depth[y * stride_y + x * stride_x] (strides in elements)
+ * with the arithmetic of sgr_depth_lookup_forward.  Every scalar mean is formed without float atomics -- one float64 partial per
+ * workgroup in the scratch, then one workgroup adds them in a fixed order -- and is bit-identical from run to run.
+ *
+ * sgr_surface_band  (:610-623, no gradient): per Gaussian c = [mu 1] * world_to_view (divided by its w), map_z = the depth lookup at c,
+ *   std_out[p] = sgr_view_std's value, close[p] = |map_z - c.z| < threshold * std_out[p] (one byte, 0 / 1).  cam_center: 3 floats on
+ *   the DEVICE.
+ * sgr_estimation_loss_*  (:644-686): per sample c = [x 1] * world_to_view, z = c.z, projected = z > znear, est = map_z(c) - z and
+ *     mode 0 ('sdf'):     | field - |est| | / s, or (( field - |est| ) / s)^2 with SGR_CL_SQUARED_EST, clamped to clamp_max; field = sdf[N]
+ *     mode 1 ('density'): | field - exp(-0.5 est^2 / beta^2) |, or its square, not clamped; field = density[N], beta[N]
+ *     on-surface term (SGR_CL_WITH_SURFACE): |est| / s, or (est / s)^2 with SGR_CL_SQUARED_SURFACE, clamped to clamp_max
+ *   with s = std[sample_idx[n]] when std != NULL (std[P]; a sample whose index is out of range is then left out) and s = scale
+ *   otherwise.  loss_estimation (with SGR_CL_WITH_EST) and loss_surface are the means over the PROJECTED samples only, n_projected[1]
+ *   (int64) their count M; M = 0 gives NaN, as torch's mean of an empty tensor.  scratch: sgr_estimation_loss_scratch_bytes(N).
+ *   The backward is one launch: it takes the forward's n_projected and the two upstream gradients by DEVICE pointer (NULL = zero) and
+ *   writes dL_dfield[N], dL_dbeta[N] (mode 1), dL_dsamples[N,3] (through z and through the lookup's projection) -- each may be NULL,
+ *   rows of samples that are not projected are zero -- and ADDS the four taps into dL_ddepth[H * W] (contiguous, zeroed by the call;
+ *   may be NULL) with float atomics, exactly as sgr_depth_lookup_backward: that one output is NOT bit-reproducible.  The clamp passes
+ *   the gradient where its input is <= clamp_max; sign(0) = 0.
+ * sgr_better_normal_*  (:688-716): with i = sample_idx[n], j = knn_idx[i, k] (knn_idx[P,K]), normals[P,3], points[P,3],
+ *   min_scaling[P] and opacities[N,K] (get_field_values' closest_gaussian_opacities; no gradient):
+ *     c = n_j * sign<n_j, n_i>,  w = opacities * |<x - mu_j, c>| / max(min_scaling_j, 1e-6)^2,  w^ = w / max(sum_k w, 1e-6),
+ *     loss = mean_n | n_i - sum_k w^_k c_k |^2.
+ *   K = 16 runs one lane per (sample, neighbour) pair, any other K one lane per sample.  The backward takes dL_dloss by DEVICE pointer.
+ *   through_normal_only != 0: only dL_dnormals[P,3] is written (dL_dpoints, dL_dsamples may be NULL); otherwise the gradient also
+ *   flows through |<x - mu_j, c>| into dL_dpoints[P,3], dL_dsamples[N,3] and c (the sign, sum_k w, min_scaling and the opacities are
+ *   constants either way).  The N (K + 1) contributions -- the pairs and each sample's own Gaussian -- are grouped by Gaussian and
+ *   summed in a fixed order, sixteen lanes per Gaussian; every row is WRITTEN, zero where nothing references the Gaussian.
+ *   N * (K + 1) < 2^32.  scratch: sgr_better_normal_forward_scratch_bytes(N, K) / sgr_better_normal_backward_scratch_bytes(N, K, P,
+ *   through_normal_only) (0 when N * (K + 1) does not fit). */
+#define SGR_CL_SQUARED_EST 1
+#define SGR_CL_SQUARED_SURFACE 2
+#define SGR_CL_WITH_EST 4
+#define SGR_CL_WITH_SURFACE 8
+int sgr_surface_band(int P, const float* points, const float* quaternions, const float* scaling, const float* world_to_view,
+                     const float* cam_center, const float* projection, const float* depth, long long stride_y, long long stride_x,
+                     int height, int width, float threshold, uint8_t* close, float* std_out, void* stream);
+size_t sgr_estimation_loss_scratch_bytes(long long N);
+int sgr_estimation_loss_forward(long long N, int P, int mode, int flags, const float* samples, const float* field, const float* beta,
+                                const int64_t* sample_idx, const float* std, float scale, float clamp_max, const float* world_to_view,
+                                const float* projection, const float* znear, const float* depth, long long stride_y, long long stride_x,
+                                int height, int width, float* loss_estimation, float* loss_surface, int64_t* n_projected, char* scratch,
+                                void* stream);
+int sgr_estimation_loss_backward(long long N, int P, int mode, int flags, const float* samples, const float* field, const float* beta,
+                                 const int64_t* sample_idx, const float* std, float scale, float clamp_max, const float* world_to_view,
+                                 const float* projection, const float* znear, const float* depth, long long stride_y, long long stride_x,
+                                 int height, int width, const int64_t* n_projected, const float* dL_dloss_estimation,
+                                 const float* dL_dloss_surface, float* dL_dfield, float* dL_dbeta, float* dL_dsamples, float* dL_ddepth,
+                                 void* stream);
+size_t sgr_better_normal_forward_scratch_bytes(long long N, int K);
+int sgr_better_normal_forward(long long N, int K, int P, const float* samples, const int64_t* sample_idx, const int64_t* knn_idx,
+                              const float* normals, const float* points, const float* min_scaling, const float* opacities, float* loss,
+                              char* scratch, void* stream);
+size_t sgr_better_normal_backward_scratch_bytes(long long N, int K, int P, int through_normal_only);
+int sgr_better_normal_backward(long long N, int K, int P, const float* samples, const int64_t* sample_idx, const int64_t* knn_idx,
+                               const float* normals, const float* points, const float* min_scaling, const float* opacities,
+                               int through_normal_only, const float* dL_dloss, float* dL_dnormals, float* dL_dpoints, float* dL_dsamples,
+                               char* scratch, void* stream);
+
 int sgr_level_set_points(int N, int K, const float* world_points, const int64_t* nbr_idx, const float* cam_center,
                          const float* centers, const float* inv_scaled_rot, const float* strengths,
                          const float* gaussian_std, int n_levels, const float* levels_host, int n_range, float range_size,

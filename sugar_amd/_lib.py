@@ -89,6 +89,16 @@ SIGNATURES = {
     "sgr_sdf_field_backward_scratch_bytes": (_sz, [_i, _i, _i]),
     "sgr_sdf_field_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
+    "sgr_surface_band": (_i, [_i] + [_vp] * 7 + [C.c_longlong, C.c_longlong, _i, _i, _f, _vp, _vp, _vp]),
+    "sgr_estimation_loss_scratch_bytes": (_sz, [C.c_longlong]),
+    "sgr_estimation_loss_forward": (_i, [C.c_longlong, _i, _i, _i] + [_vp] * 5 + [_f, _f] + [_vp] * 4 + [C.c_longlong, C.c_longlong, _i, _i]
+                                    + [_vp] * 5),
+    "sgr_estimation_loss_backward": (_i, [C.c_longlong, _i, _i, _i] + [_vp] * 5 + [_f, _f] + [_vp] * 4 + [C.c_longlong, C.c_longlong, _i, _i]
+                                     + [_vp] * 8),
+    "sgr_better_normal_forward_scratch_bytes": (_sz, [C.c_longlong, _i]),
+    "sgr_better_normal_forward": (_i, [C.c_longlong, _i, _i] + [_vp] * 10),
+    "sgr_better_normal_backward_scratch_bytes": (_sz, [C.c_longlong, _i, _i, _i]),
+    "sgr_better_normal_backward": (_i, [C.c_longlong, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 6),
     "sgr_scaled_rotation_forward": (_i, [_i, _vp, _vp, _i, _vp, _vp]),
     "sgr_scaled_rotation_backward": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sgr_pack_gaussians": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),

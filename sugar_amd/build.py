@@ -41,6 +41,7 @@ SOURCES = {
     "field.hip": [],
     "group.hip": [],
     "sdf_regulariser.hip": [],
+    "coarse_loss.hip": [],
     "pick.hip": [],
     "capi.hip": [],
     "train.hip": [],

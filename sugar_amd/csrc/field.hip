@@ -408,18 +408,7 @@ __global__ void __launch_bounds__(256) k_view_std(int P, const float* __restrict
 {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= P) return;
-    const float4 q = reinterpret_cast<const float4*>(quats)[g];
-    const float r = q.x, x = q.y, y = q.z, z = q.w;
-    float vx = cam_center[0] - centers[3 * (size_t)g], vy = cam_center[1] - centers[3 * (size_t)g + 1],
-          vz = cam_center[2] - centers[3 * (size_t)g + 2];
-    const float inv = 1.0f / fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
-    vx *= inv; vy *= inv; vz *= inv;
-    // rows of R^T = columns of R
-    const float ox = (1 - 2 * (y * y + z * z)) * vx + 2 * (x * y + r * z) * vy + 2 * (x * z - r * y) * vz;
-    const float oy = 2 * (x * y - r * z) * vx + (1 - 2 * (x * x + z * z)) * vy + 2 * (y * z + r * x) * vz;
-    const float oz = 2 * (x * z + r * y) * vx + 2 * (y * z - r * x) * vy + (1 - 2 * (x * x + y * y)) * vz;
-    const float sx = scaling[3 * (size_t)g] * ox, sy = scaling[3 * (size_t)g + 1] * oy, sz = scaling[3 * (size_t)g + 2] * oz;
-    out[g] = sqrtf(sx * sx + sy * sy + sz * sz);
+    out[g] = view_std_of(g, centers, quats, scaling, cam_center);
 }
 
 // World points of picked pixels (:1934-1959).  The reference lays an NDC grid over the image (x = W/m - 2 col / (m - 1), +x to the

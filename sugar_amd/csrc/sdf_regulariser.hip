@@ -17,6 +17,7 @@
 #include "../../include/sugar_raster.h"
 #include "sgr_device.h"
 #include "sgr_group.h"
+#include "sgr_depth_lookup.h"
 
 namespace {
 
@@ -144,32 +145,7 @@ __global__ void __launch_bounds__(256) k_smallest_axis_bwd(int P, const float* _
 }
 
 // -------------------------------------------------------------------------------------------------------------- depth lookup
-struct Lookup {
-    float c3, ndc_x, ndc_y;   // w of the projection, and x / w, y / w
-    float ix, iy;             // pixel coordinates after the clamp to the image
-    float mx, my;             // d(ix) / d(ndc_x), d(iy) / d(ndc_y): 0 where the clamp is active
-    bool finite;
-};
-
-__device__ __forceinline__ Lookup lookup_coords(float x, float y, float z, const float* __restrict__ Pm, int H, int W)
-{
-    Lookup L;
-    const float c0 = x * Pm[0] + y * Pm[4] + z * Pm[8] + Pm[12];
-    const float c1 = x * Pm[1] + y * Pm[5] + z * Pm[9] + Pm[13];
-    L.c3 = x * Pm[3] + y * Pm[7] + z * Pm[11] + Pm[15];
-    L.ndc_x = c0 / L.c3; L.ndc_y = c1 / L.c3;
-    const float m = (float)(H < W ? H : W);
-    const float fx = -1.0f * m / (float)W, fy = -1.0f * m / (float)H;
-    const float gx = fx * L.ndc_x, gy = fy * L.ndc_y;
-    float ix = ((gx + 1.0f) * (float)W - 1.0f) / 2.0f, iy = ((gy + 1.0f) * (float)H - 1.0f) / 2.0f;
-    L.mx = fx * ((float)W / 2.0f); L.my = fy * ((float)H / 2.0f);
-    if (ix <= 0.f) { ix = 0.f; L.mx = 0.f; } else if (ix >= (float)(W - 1)) { ix = (float)(W - 1); L.mx = 0.f; }
-    if (iy <= 0.f) { iy = 0.f; L.my = 0.f; } else if (iy >= (float)(H - 1)) { iy = (float)(H - 1); L.my = 0.f; }
-    L.finite = (ix == ix) && (iy == iy);   // NaN coordinates reach no tap (grid_sample: every tap out of bounds)
-    L.ix = ix; L.iy = iy;
-    return L;
-}
-
+// (the per-point arithmetic is sgr_depth_lookup.h: coarse_loss.hip evaluates the same lookup inside its loss kernels)
 __global__ void __launch_bounds__(256) k_depth_lookup_fwd(long long M, const float* __restrict__ pts, const float* __restrict__ Pm,
                                                           const float* __restrict__ depth, long long sy, long long sx, int H, int W,
                                                           float* __restrict__ out)
@@ -177,17 +153,7 @@ __global__ void __launch_bounds__(256) k_depth_lookup_fwd(long long M, const flo
     const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
     const Lookup L = lookup_coords(pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], Pm, H, W);
-    float v = 0.f;
-    if (L.finite) {
-        const int x0 = (int)floorf(L.ix), y0 = (int)floorf(L.iy), x1 = x0 + 1, y1 = y0 + 1;   // in [0, W-1] x [0, H-1] after the clamp
-        const float wx1 = L.ix - (float)x0, wx0 = (float)x1 - L.ix, wy1 = L.iy - (float)y0, wy0 = (float)y1 - L.iy;
-        const bool bx1 = x1 < W, by1 = y1 < H;
-        v += depth[y0 * sy + x0 * sx] * (wx0 * wy0);
-        if (bx1) v += depth[y0 * sy + x1 * sx] * (wx1 * wy0);
-        if (by1) v += depth[y1 * sy + x0 * sx] * (wx0 * wy1);
-        if (bx1 && by1) v += depth[y1 * sy + x1 * sx] * (wx1 * wy1);
-    }
-    out[n] = v;
+    out[n] = lookup_value(L, depth, sy, sx, H, W);
 }
 
 __global__ void __launch_bounds__(256) k_depth_lookup_bwd(long long M, const float* __restrict__ pts, const float* __restrict__ Pm,
@@ -198,39 +164,9 @@ __global__ void __launch_bounds__(256) k_depth_lookup_bwd(long long M, const flo
     const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
     if (n >= M) return;
     const Lookup L = lookup_coords(pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], Pm, H, W);
-    const float g = g_out[n];
-    float gix = 0.f, giy = 0.f;
-    if (L.finite) {
-        const int x0 = (int)floorf(L.ix), y0 = (int)floorf(L.iy), x1 = x0 + 1, y1 = y0 + 1;
-        const float wx1 = L.ix - (float)x0, wx0 = (float)x1 - L.ix, wy1 = L.iy - (float)y0, wy0 = (float)y1 - L.iy;
-        const bool bx1 = x1 < W, by1 = y1 < H;
-        const float v00 = depth[y0 * sy + x0 * sx];
-        gix -= v00 * wy0 * g; giy -= v00 * wx0 * g;
-        if (ddepth) atomicAdd(&ddepth[(size_t)y0 * W + x0], wx0 * wy0 * g);
-        if (bx1) {
-            const float v = depth[y0 * sy + x1 * sx];
-            gix += v * wy0 * g; giy -= v * wx1 * g;
-            if (ddepth) atomicAdd(&ddepth[(size_t)y0 * W + x1], wx1 * wy0 * g);
-        }
-        if (by1) {
-            const float v = depth[y1 * sy + x0 * sx];
-            gix -= v * wy1 * g; giy += v * wx0 * g;
-            if (ddepth) atomicAdd(&ddepth[(size_t)y1 * W + x0], wx0 * wy1 * g);
-        }
-        if (bx1 && by1) {
-            const float v = depth[y1 * sy + x1 * sx];
-            gix += v * wy1 * g; giy += v * wx1 * g;
-            if (ddepth) atomicAdd(&ddepth[(size_t)y1 * W + x1], wx1 * wy1 * g);
-        }
-    }
-    if (dpts) {
-        const float dnx = L.mx * gix, dny = L.my * giy;          // dL/d ndc
-        const float dc0 = dnx / L.c3, dc1 = dny / L.c3;
-        const float dc3 = -(L.ndc_x * dnx + L.ndc_y * dny) / L.c3;
-        dpts[3 * n] = Pm[0] * dc0 + Pm[1] * dc1 + Pm[3] * dc3;
-        dpts[3 * n + 1] = Pm[4] * dc0 + Pm[5] * dc1 + Pm[7] * dc3;
-        dpts[3 * n + 2] = Pm[8] * dc0 + Pm[9] * dc1 + Pm[11] * dc3;
-    }
+    float gix, giy;
+    lookup_value_bwd(L, depth, sy, sx, H, W, g_out[n], ddepth, gix, giy);
+    if (dpts) lookup_coords_bwd(L, Pm, gix, giy, dpts[3 * n], dpts[3 * n + 1], dpts[3 * n + 2]);
 }
 
 }  // namespace

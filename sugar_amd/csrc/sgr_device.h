@@ -56,6 +56,26 @@ __device__ __forceinline__ void quat_M(float r, float i, float j, float k, float
     M[6] = i * k - j * r;    M[7] = j * k + i * r;     M[8] = -(i * i + j * j);
 }
 
+// gaussian_std of sugar_model.py:1971-1972 (and coarse_sdf.py:612-620) for Gaussian g: | scales (.) R(q)^T normalize(cam_center - centre) |
+// with the unit quaternions the model hands out (`quaternion_apply(quaternion_invert(q), v)`; F.normalize: v / max(|v|, 1e-12)).
+// Shared by k_view_std of field.hip and the surface band of coarse_loss.hip.
+__device__ __forceinline__ float view_std_of(size_t g, const float* __restrict__ centers, const float* __restrict__ quats,
+                                             const float* __restrict__ scaling, const float* __restrict__ cam_center)
+{
+    const float4 q = reinterpret_cast<const float4*>(quats)[g];
+    const float r = q.x, x = q.y, y = q.z, z = q.w;
+    float vx = cam_center[0] - centers[3 * g], vy = cam_center[1] - centers[3 * g + 1],
+          vz = cam_center[2] - centers[3 * g + 2];
+    const float inv = 1.0f / fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
+    vx *= inv; vy *= inv; vz *= inv;
+    // rows of R^T = columns of R
+    const float ox = (1 - 2 * (y * y + z * z)) * vx + 2 * (x * y + r * z) * vy + 2 * (x * z - r * y) * vz;
+    const float oy = 2 * (x * y - r * z) * vx + (1 - 2 * (x * x + z * z)) * vy + 2 * (y * z + r * x) * vz;
+    const float oz = 2 * (x * z + r * y) * vx + 2 * (y * z - r * x) * vy + (1 - 2 * (x * x + y * y)) * vz;
+    const float sx = scaling[3 * g] * ox, sy = scaling[3 * g + 1] * oy, sz = scaling[3 * g + 2] * oz;
+    return sqrtf(sx * sx + sy * sy + sz * sz);
+}
+
 // a row index as Python reads it: negative values wrap once (the caller checks 0 <= result < P)
 __device__ __forceinline__ long long wrap_row(long long i, int P) { return i < 0 ? i + P : i; }
 
