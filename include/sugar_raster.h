@@ -679,6 +679,39 @@ int sgr_better_normal_backward(long long N, int K, int P, const float* samples, 
                                int through_normal_only, const float* dL_dloss, float* dL_dnormals, float* dL_dpoints, float* dL_dsamples,
                                char* scratch, void* stream);
 
+/* sgr_opacity_entropy_*  (coarse_sdf.py:543-551; csrc/coarse_loss.hip, additive): loss = the mean over the rows with visible[p] != 0
+ *   (one byte per row) of (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10), o = opacities[P], in that operation order and reduced
+ *   as the means above; n_visible[1] (int64) is their count, formed on the device; no visible row gives NaN.  The backward is one
+ *   launch: it takes the forward's n_visible and the upstream gradient by DEVICE pointer and writes every row of dL_dopacities[P], zero
+ *   where invisible.  scratch: sgr_opacity_entropy_scratch_bytes(P). */
+size_t sgr_opacity_entropy_scratch_bytes(int P);
+int sgr_opacity_entropy_forward(int P, const float* opacities, const uint8_t* visible, float* loss, int64_t* n_visible, char* scratch,
+                                void* stream);
+int sgr_opacity_entropy_backward(int P, const float* opacities, const uint8_t* visible, const int64_t* n_visible, const float* dL_dloss,
+                                 float* dL_dopacities, void* stream);
+
+/* ---- the coarse stage's default sample draws on the device (csrc/coarse_draw.hip; added under ABI version 4, additive) ---------------
+ * SuGaR.sample_points_in_gaussians(mask=..., probabilities_proportional_to_volume=False), sugar_model.py:900-926, up to the arithmetic
+ * of sgr_sample_transform_forward: every sample picks one Gaussian uniformly among the rows with mask[p] != 0 (one byte per row) and
+ * takes three standard normals.  No host synchronisation: the masked rows are compacted in ascending order into the scratch, their
+ * count goes to n_masked[1] (int64, on the device), and one lane per sample draws.  P < 2^31, N < 2^32.
+ *
+ * The stream (restated bit for bit in tests/coarse_draw_restatement.py): Philox4x32-10 with the standard constants (multipliers
+ * 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85); key = (seed lo32, seed hi32); sample n uses the two blocks with the
+ * counters (c lo32, c hi32, call lo32, call hi32), c = 2 n and c = 2 n + 1.
+ *   block 0 -> r0..r3:  j = (uint64(r0) * n_masked) >> 32,  sample_idx[n] = the j-th masked row in ascending order;
+ *                       (r1, r2) one Box-Muller pair: noise[n,0] = rho cos(theta), noise[n,1] = rho sin(theta)
+ *   block 1 -> r0, r1:  a second pair, whose cosine branch is noise[n,2]
+ *   u(r) = ((r >> 8) + 0.5) * 2^-24, rho = sqrt(-2 log u(first word)), theta = 2 pi u(second word), in float32 with the accurate
+ *   logf / sincosf and every operation rounded on its own.  u is never 0; (r >> 8) + 0.5 is exact in float32 only while r < 2^31 --
+ *   above, the sum rounds to even, and the one word pattern r >> 8 = 2^24 - 1 gives u = 1 (rho = 0): harmless, and the restatement
+ *   does the same.
+ * n_masked == 0: sample_idx = 0 and noise = 0 everywhere; the caller skips the regulariser (coarse_sdf.py:626).
+ * scratch: sgr_draw_samples_scratch_bytes(P). */
+size_t sgr_draw_samples_scratch_bytes(int P);
+int sgr_draw_samples(int P, const uint8_t* mask, long long N, uint64_t seed, uint64_t call, int64_t* sample_idx, float* noise,
+                     int64_t* n_masked, char* scratch, void* stream);
+
 int sgr_level_set_points(int N, int K, const float* world_points, const int64_t* nbr_idx, const float* cam_center,
                          const float* centers, const float* inv_scaled_rot, const float* strengths,
                          const float* gaussian_std, int n_levels, const float* levels_host, int n_range, float range_size,

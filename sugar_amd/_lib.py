@@ -99,6 +99,11 @@ SIGNATURES = {
     "sgr_better_normal_forward": (_i, [C.c_longlong, _i, _i] + [_vp] * 10),
     "sgr_better_normal_backward_scratch_bytes": (_sz, [C.c_longlong, _i, _i, _i]),
     "sgr_better_normal_backward": (_i, [C.c_longlong, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 6),
+    "sgr_opacity_entropy_scratch_bytes": (_sz, [_i]),
+    "sgr_opacity_entropy_forward": (_i, [_i] + [_vp] * 6),
+    "sgr_opacity_entropy_backward": (_i, [_i] + [_vp] * 6),
+    "sgr_draw_samples_scratch_bytes": (_sz, [_i]),
+    "sgr_draw_samples": (_i, [_i, _vp, C.c_longlong, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "sgr_scaled_rotation_forward": (_i, [_i, _vp, _vp, _i, _vp, _vp]),
     "sgr_scaled_rotation_backward": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sgr_pack_gaussians": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),

@@ -7,6 +7,7 @@ of `sample_points_in_gaussians`, `get_field_values` and `get_normals`, as three 
                         samples in front of the camera, and their count M                                       :644-686
     better_normal_loss  the "better normal" mean over the samples                                               :688-716
     regulariser_terms   the whole of :606-716 for any object with SuGaR's attributes                            :606-716
+    opacity_entropy     the entropy term the loop adds before the regulariser starts (sgr_opacity_entropy_*)    :543-551
 
 GPU tensors only; the HIP library must be built.  No operation synchronises with the host; camera matrices (pytorch3d's row vectors)
 and `znear` are read on the device; the depth map is read through its strides.  The scalar means and every per-Gaussian gradient are
@@ -202,6 +203,41 @@ def better_normal_loss(samples, sample_idx, knn_idx, normals, points, min_scalin
         raise RuntimeError("better_normal_loss: N * (K + 1) must stay below 2^32")
     return _BetterNormal.apply(_plain(samples), _plain(normals), _plain(points), sample_idx, knn_idx, _plain(min_scaling), opacities,
                                through_normal_only)
+
+
+class _OpacityEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, opacities, visible):
+        o = _f32c(opacities.reshape(-1))
+        vis = visible.reshape(-1).contiguous()
+        P, dev = o.shape[0], o.device
+        loss = torch.empty((), device=dev)
+        count = torch.empty((), dtype=torch.int64, device=dev)
+        scratch = _scratch(_lib.load().sgr_opacity_entropy_scratch_bytes(P), dev)
+        call("sgr_opacity_entropy_forward", dev, P, ptr(o), ptr(vis), ptr(loss), ptr(count), ptr(scratch))
+        ctx.save_for_backward(o, vis, count)
+        ctx.shape = opacities.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        o, vis, count = ctx.saved_tensors
+        P, dev = o.shape[0], o.device
+        do = torch.empty(P, device=dev)
+        call("sgr_opacity_entropy_backward", dev, P, ptr(o), ptr(vis), ptr(count), ptr(_f32c(g)), ptr(do))
+        return do.reshape(ctx.shape), None
+
+
+def opacity_entropy(opacities, visible):
+    """The entropy term of coarse_sdf.py:543-551 as a 0-dim device tensor:
+    `(-o * log(o + 1e-10) - (1 - o) * log(1 - o + 1e-10))[visible].mean()` for opacities [P,1] or [P] and the bool [P] mask `visible`
+    (the trainer's `radii > 0`).  The visible rows are counted on the device; with none the value is NaN (torch's mean of an empty
+    tensor) and the gradient zero.  Differentiable w.r.t. the opacities: every row of the gradient is written, zero where invisible."""
+    need_gpu("opacity_entropy", opacities=opacities, visible=visible)
+    P = visible.numel()
+    if visible.dtype != torch.bool or opacities.numel() != P or P < 1 or opacities.dim() > 2:
+        raise RuntimeError("opacity_entropy: expected opacities[P,1] or [P] and a bool visible[P], P >= 1")
+    return _OpacityEntropy.apply(_plain(opacities), visible)
 
 
 def regulariser_terms(sugar, fov_camera, depth, visibility_filter, *, sdf_estimation_mode: str = "sdf",

@@ -14,6 +14,9 @@
 //                       w^ = w / max(sum_k w, 1e-6) (the sum detached),  loss_n = | n_s - sum_k w^_k c_k |^2, averaged over N.
 //                       K = 16: one lane per (sample, neighbour) pair, the sixteen pairs of a sample in one DPP row; any other K: one
 //                       lane per sample.
+//   opacity entropy   : :543-551, the term the loop adds before the regulariser starts.  One lane per Gaussian:
+//                       (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10), averaged over the visible rows; their count is formed on
+//                       the device, no visible row gives NaN.  The backward writes every row, zero where invisible.
 //
 // Reductions: every workgroup writes ONE float64 partial per term into the scratch, one workgroup then adds them in a fixed order and
 // divides: no float atomics, the same bits every run.  Per-Gaussian gradients of the better-normal loss: every (sample, neighbour)
@@ -433,6 +436,41 @@ __global__ void __launch_bounds__(256) k_normal_rows_gather(int P, const float* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------- opacity entropy
+// coarse_sdf.py:548-551 for one row, in the trainer's operation order: (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10)
+__global__ void __launch_bounds__(256) k_entropy_fwd(int P, const float* __restrict__ opac, const uint8_t* __restrict__ visible,
+                                                     double* __restrict__ partial, size_t n_blocks)
+{
+    __shared__ double s_wave[4];
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;   // (P up to 2^31 - 1: the last workgroup's rows do not wrap)
+    double t_sum = 0.0, t_cnt = 0.0;
+    if (g < P && visible[g]) {
+        const float o = opac[g], b = 1.f - o;
+        t_sum = (double)((-o) * logf(o + 1e-10f) - b * logf(b + 1e-10f));
+        t_cnt = 1.0;
+    }
+    t_sum = block_sum256(t_sum, s_wave);
+    t_cnt = block_sum256(t_cnt, s_wave);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = t_sum; partial[n_blocks + blockIdx.x] = t_cnt; }
+}
+
+// every row is written: (g / n_visible) d/do of the row's term where visible, zero elsewhere
+__global__ void __launch_bounds__(256) k_entropy_bwd(int P, const float* __restrict__ opac, const uint8_t* __restrict__ visible,
+                                                     const long long* __restrict__ n_visible, const float* __restrict__ g_loss,
+                                                     float* __restrict__ dopac)
+{
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;   // (P up to 2^31 - 1: the last workgroup's rows do not wrap)
+    if (g >= P) return;
+    float d = 0.f;
+    if (visible[g]) {
+        const float gm = g_loss[0] / (float)n_visible[0];
+        const float o = opac[g], b = 1.f - o, a = o + 1e-10f, c = b + 1e-10f;
+        // first term: d/do [(-o) log a] = -log a - o / a;   second: d/do [-(b log c)] = log c + b / c
+        d = (-gm * logf(a) + (gm * (-o)) / a) + (gm * logf(c) + (gm * b) / c);
+    }
+    dopac[g] = d;
+}
+
 bool est_args_ok(const EstArgs& a, int mode)
 {
     return a.N > 0 && (unsigned long long)a.N <= 0xFFFFFFFFull && (mode == 0 || mode == 1) && a.x && a.V && a.Pm && a.znear && a.depth &&
@@ -498,6 +536,29 @@ int sgr_estimation_loss_backward(long long N, int P, int mode, int flags, const 
     else
         hipLaunchKernelGGL(k_estimation_bwd<false>, dim3(blocks256((size_t)N)), dim3(256), 0, s, a, M, dL_dloss_estimation, dL_dloss_surface,
                            dL_dfield, dL_dbeta, dL_dsamples, dL_ddepth);
+    return sgr_launch_status();
+}
+
+size_t sgr_opacity_entropy_scratch_bytes(int P) { return cl_entropy_scratch_bytes(P); }
+
+int sgr_opacity_entropy_forward(int P, const float* opacities, const uint8_t* visible, float* loss, int64_t* n_visible, char* scratch,
+                                void* stream)
+{
+    if (P <= 0 || !opacities || !visible || !loss || !n_visible || !scratch) return SGR_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = cl_blocks((size_t)P, 256);
+    double* partial = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(k_entropy_fwd, dim3((unsigned)nb), dim3(256), 0, s, P, opacities, visible, partial, nb);
+    hipLaunchKernelGGL(k_finish_means, dim3(1), dim3(256), 0, s, partial, nb, 2, 1, 0.0, loss, nullptr, reinterpret_cast<long long*>(n_visible));
+    return sgr_launch_status();
+}
+
+int sgr_opacity_entropy_backward(int P, const float* opacities, const uint8_t* visible, const int64_t* n_visible, const float* dL_dloss,
+                                 float* dL_dopacities, void* stream)
+{
+    if (P <= 0 || !opacities || !visible || !n_visible || !dL_dloss || !dL_dopacities) return SGR_E_INVALID;
+    hipLaunchKernelGGL(k_entropy_bwd, dim3(blocks256((size_t)P)), dim3(256), 0, (hipStream_t)stream, P, opacities, visible,
+                       reinterpret_cast<const long long*>(n_visible), dL_dloss, dL_dopacities);
     return sgr_launch_status();
 }
 

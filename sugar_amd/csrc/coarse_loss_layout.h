@@ -16,6 +16,9 @@ static inline size_t cl_blocks(size_t n, size_t per_block) { return (n + per_blo
 static inline size_t cl_estimation_blocks(long long N) { return cl_blocks((size_t)(N > 0 ? N : 0), 256); }
 static inline size_t cl_estimation_scratch_bytes(long long N) { return cl_align(3 * cl_estimation_blocks(N) * sizeof(double)); }
 
+// opacity entropy: partial f64[2][ceil(P / 256)]   (the sum of the visible rows' terms | their count)
+static inline size_t cl_entropy_scratch_bytes(int P) { return cl_align(2 * cl_blocks((size_t)(P > 0 ? P : 0), 256) * sizeof(double)); }
+
 static inline size_t cl_normal_blocks(long long N, int K) { return cl_blocks((size_t)(N > 0 ? N : 0), K == 16 ? 16 : 256); }
 static inline size_t cl_normal_fwd_scratch_bytes(long long N, int K) { return cl_align(cl_normal_blocks(N, K) * sizeof(double)); }
 
