@@ -182,6 +182,12 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user,
 #define SGR_FLAG_NO_DEEP 32   /* this call: one wave per block whatever the hint says (a caller that knows its lists are short saves the
                                  side stream's fork and join: sgr_trainer_step sets it unless the camera's last visit left a hint
                                  above the threshold -- host header word 9, second copy, carries the largest hint written) */
+/* SGR_FLAG_REACH (used by sgr_trainer_step): the blend kernels of this forward also set the reach flag -- one byte per Gaussian at
+ * sgr_geom_reach_offset_bytes(P) of the geometry scratch -- of every Gaussian that survives the exact cull of any 8x8 block.  The
+ * blend backward can reach no other Gaussian, so the SH-Adam step of an unflagged one needs nothing the backward computes
+ * (sgr_sh_adam_zero_grad).  The forward only ever sets flags; sgr_sh_adam_from_views_masked clears them.  Such a forward blends every
+ * block with the one-wave kernel, whatever sgr_set_deep_min says: the eight-wave kernel for long lists does not flag. */
+#define SGR_FLAG_REACH 64
 void sgr_set_deep_min(int entries);
 int sgr_get_deep_min(void);
 void sgr_set_exact_alpha(int on);
@@ -300,6 +306,28 @@ int sgr_sh_adam_from_views_ex(int P, int n_views, int D, int M, const float* mea
                               const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq,
                               float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
                               float* dmean_extra, void* stream);
+
+/* SH-Adam split by reach flag (SGR_FLAG_REACH; M == 16 and 16-byte aligned buffers only, SGR_E_INVALID otherwise).  reach[P]: one byte
+ * per Gaussian.  sgr_sh_adam_zero_grad applies the update of sgr_sh_adam_from_views with a gradient of zero to every Gaussian whose
+ * flag is 0 and leaves the others alone; sgr_sh_adam_from_views_masked updates the Gaussians whose flag is not 0 from the colour
+ * gradients, leaves the others alone and sets every flag to 0.  One after the other they leave sh_params and both moments bit-identical
+ * to one sgr_sh_adam_from_views call, provided the colour gradient of every unflagged Gaussian is +0 in every view -- which holds for
+ * the flags a forward wrote.  guard_header (device, or NULL) / guard_capacity: the header of the forward the step belongs to and its
+ * list capacity; when that forward was invalid (sgr_trainer_forward_valid) both calls change nothing. */
+int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                          float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                          const uint32_t* guard_header, uint32_t guard_capacity, void* stream);
+int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
+                                  const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq,
+                                  float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                                  uint8_t* reach, const uint32_t* guard_header, uint32_t guard_capacity, void* stream);
+/* Process-wide switch of the train step (sgr_trainer_step with all four phases, one view, M == 16): the zero-gradient half runs as extra
+ * workgroups inside the blend backward's launch, the masked half in the optimiser's place.  SGR_ADAM_OVERLAP=0 / 1 in the environment
+ * sets the default; SGR_ADAM_OVERLAP_K the Adam workgroups behind every 32 blend workgroups (a multiple of 8, default 24).
+ * 2 is a verification mode: the forward sets the flags, the dense kernel runs and nothing clears them. */
+void sgr_set_adam_overlap(int on);
+int sgr_get_adam_overlap(void);
+size_t sgr_geom_reach_offset_bytes(int P);
 
 /* Rasterizer::markVisible, DGR/cuda_rasterizer/rasterizer.h:24-29 / rasterizer_impl.cu:141-153.
  * present[P] is one byte per Gaussian (bool). */

@@ -51,6 +51,12 @@ SIGNATURES = {
     "sgr_sh_grad_from_views": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp]),
     "sgr_sh_adam_from_views": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "sgr_sh_adam_from_views_ex": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
+    "sgr_sh_adam_zero_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, C.c_uint32, _vp]),
+    "sgr_sh_adam_from_views_masked": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _vp,
+                                           C.c_uint32, _vp]),
+    "sgr_set_adam_overlap": (None, [_i]),
+    "sgr_get_adam_overlap": (_i, []),
+    "sgr_geom_reach_offset_bytes": (_sz, [_i]),
     "sgr_geom_bytes": (_sz, [_i]),
     "sgr_img_bytes": (_sz, [_i, _i]),
     "sgr_binning_bytes": (_sz, [_i64, _i, _i]),

@@ -18,6 +18,7 @@
 // 36-byte atomic request into a 64-byte accumulator record instead of the reference's up to 64 x 9 float atomics
 // (backward.cu:523-554).
 #include "sgr_common.h"
+#include "sh_adam_update.h"
 #include "tile_order.h"
 
 namespace {
@@ -348,7 +349,7 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
                                                     uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_maxc,
                                                     uint32_t* __restrict__ tile_walked, float* __restrict__ out_color,
                                                     unsigned long long* __restrict__ blk_mask, uint32_t* __restrict__ blk_nb,
-                                                    uint32_t* __restrict__ header, uint32_t list_cap,
+                                                    uint32_t* __restrict__ header, uint32_t list_cap, uint8_t* __restrict__ reach,
                                                     const uint32_t* __restrict__ tile_need, const uint32_t* __restrict__ launch_order,
                                                     uint32_t* __restrict__ repair_flag, uint32_t* __restrict__ repair_list, uint32_t deep_min = 0u)
 {
@@ -419,6 +420,7 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
     // registers across the walk.  For the one wave of a tile that walks thousands of entries the gather's round trip is then off
     // the chain; see DESIGN.md for what it did to the metric workload and to config 4)
     float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0;
+    uint32_t id_pref = id_next;  // whose records p0 .. p2 hold
     if (total > 0) {
         const float4* rp0 = reinterpret_cast<const float4*>(rec + id_next);
         p0 = rp0[0]; p1 = rp0[1]; p2 = rp0[2];
@@ -429,6 +431,8 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
     for (int base = 0; base < total && live != 0ull; base += 64) {
 #ifdef SGR_FWD_PREFETCH_RECORDS
         const float4 v0 = p0, v1 = p1, v2 = p2;
+        const uint32_t id_cur = id_pref;
+        id_pref = id_next;
         {
             const float4* rp = reinterpret_cast<const float4*>(rec + id_next);   // batch b + 1 (clamped ids past the end: a cached line)
             p0 = rp[0]; p1 = rp[1]; p2 = rp[2];
@@ -436,7 +440,8 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
         id_next = id_next2;
         id_next2 = point_list[r0 + (uint32_t)min(base + 192 + lane, total - 1)];
 #else
-        const float4* rp = reinterpret_cast<const float4*>(rec + id_next);
+        const uint32_t id_cur = id_next;  // (kept for the reach flag below: id_next moves on)
+        const float4* rp = reinterpret_cast<const float4*>(rec + id_cur);
         const float4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
         id_next = id_next2;
         id_next2 = point_list[r0 + (uint32_t)min(base + 128 + lane, total - 1)];
@@ -465,6 +470,9 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
             }
 #endif
             *reinterpret_cast<float2*>(e + 2) = make_float2(v2.z, __uint_as_float((uint32_t)(base + lane + 1)));
+            // reach flag (sh_adam_update.h): this Gaussian has a survivor bit in the mask written below, so the blend backward may reach
+            // it.  The same value from many waves: a plain byte store.
+            if (reach) reach[id_cur] = 1;
         }
         if (lane == 0) my_mask[4 * (size_t)n_batches] = m;
         n_batches++;
@@ -526,26 +534,26 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
         uint32_t *__restrict__ tile_maxc, uint32_t *__restrict__ tile_walked, float *__restrict__ out_color,                         \
         unsigned long long *__restrict__ blk_mask, uint32_t *__restrict__ blk_nb, uint32_t *__restrict__ header, uint32_t list_cap
 #define SGR_FWD_ARGS W, H, gx, T_tiles, tile_start, point_list, rec, bg, final_T, n_contrib, tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, list_cap
-__global__ void __launch_bounds__(64) k_blend_fwd_w(SGR_FWD_PARAMS, const uint32_t* __restrict__ tile_need, const uint32_t* __restrict__ launch_order,
+__global__ void __launch_bounds__(64) k_blend_fwd_w(SGR_FWD_PARAMS, uint8_t* __restrict__ reach, const uint32_t* __restrict__ tile_need, const uint32_t* __restrict__ launch_order,
                                                     uint32_t* __restrict__ repair_flag, uint32_t* __restrict__ repair_list, uint32_t deep_min)
 {
-    blend_fwd_body<false, false>(SGR_FWD_ARGS, tile_need, launch_order, repair_flag, repair_list, deep_min);
+    blend_fwd_body<false, false>(SGR_FWD_ARGS, reach, tile_need, launch_order, repair_flag, repair_list, deep_min);
 }
 // (the exact-alpha variant: SGR_FWD_BODY_X)
-__global__ void __launch_bounds__(64) k_blend_fwd_wx(SGR_FWD_PARAMS, const uint32_t* __restrict__ tile_need, const uint32_t* __restrict__ launch_order,
+__global__ void __launch_bounds__(64) k_blend_fwd_wx(SGR_FWD_PARAMS, uint8_t* __restrict__ reach, const uint32_t* __restrict__ tile_need, const uint32_t* __restrict__ launch_order,
                                                      uint32_t* __restrict__ repair_flag, uint32_t* __restrict__ repair_list, uint32_t deep_min)
 {
-    blend_fwd_body<false, true>(SGR_FWD_ARGS, tile_need, launch_order, repair_flag, repair_list, deep_min);
+    blend_fwd_body<false, true>(SGR_FWD_ARGS, reach, tile_need, launch_order, repair_flag, repair_list, deep_min);
 }
 
 // the repair pass of the walk hint (a kernel name of its own, so that a trace tells the gated, usually empty launch from the blend)
-__global__ void __launch_bounds__(64) k_blend_fwd_repair(SGR_FWD_PARAMS, const uint32_t* __restrict__ repair_list)
+__global__ void __launch_bounds__(64) k_blend_fwd_repair(SGR_FWD_PARAMS, uint8_t* __restrict__ reach, const uint32_t* __restrict__ repair_list)
 {
-    blend_fwd_body<true, false>(SGR_FWD_ARGS, nullptr, repair_list, nullptr, nullptr);
+    blend_fwd_body<true, false>(SGR_FWD_ARGS, reach, nullptr, repair_list, nullptr, nullptr);
 }
-__global__ void __launch_bounds__(64) k_blend_fwd_repairx(SGR_FWD_PARAMS, const uint32_t* __restrict__ repair_list)
+__global__ void __launch_bounds__(64) k_blend_fwd_repairx(SGR_FWD_PARAMS, uint8_t* __restrict__ reach, const uint32_t* __restrict__ repair_list)
 {
-    blend_fwd_body<true, true>(SGR_FWD_ARGS, nullptr, repair_list, nullptr, nullptr);
+    blend_fwd_body<true, true>(SGR_FWD_ARGS, reach, nullptr, repair_list, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -970,12 +978,30 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
               const char* __restrict__ binning, const uint32_t* __restrict__ blk_nb, const GeomRec* __restrict__ rec,
               const float* __restrict__ bg, const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib,
               const float* __restrict__ dL_dpix, float* __restrict__ acc, const uint32_t* __restrict__ tile_order,
-              const uint32_t* __restrict__ header, uint32_t list_cap)
+              const uint32_t* __restrict__ header, uint32_t list_cap, const SgrShAdamJob& job)
 {
     __shared__ __attribute__((aligned(16))) float s_q[(BW_QCAP + 1) * BW_ENTRY_DW];  // (+1: phase A's look-ahead)
+    int wg = blockIdx.x;
+    // The ride-along (sh_adam_update.h): with a job the grid is [ n_with x (32 blend workgroups, k Adam workgroups) | the other blend
+    // groups | the Adam workgroups left over ].  This kernel leaves HBM nearly idle and the zero-gradient Adam of the Gaussians the
+    // forward never flagged is pure streaming that waits for nothing the backward computes.  k is a multiple of 8, so a blend workgroup
+    // keeps its XCD (sgr_slot_of_workgroup).  Wave-uniform: blockIdx and kernel arguments only.
+    if (job.P > 0) {
+        const int per = 32 + job.k, n1 = job.n_with * per;
+        int adam = -1;
+        if (wg < n1) {
+            const int q = wg / per, r = wg - q * per;
+            if (r < 32) wg = q * 32 + r; else adam = q * job.k + (r - 32);
+        } else {
+            const int w2 = wg - n1, rest = (job.n_groups - job.n_with) * 32;
+            if (w2 < rest) wg = job.n_with * 32 + w2; else adam = job.n_with * job.k + (w2 - rest);
+        }
+        // (four float4 steps per round of loads, as in k_sh_adam_from_views: six cost the kernel a wave per SIMD -- 110 VGPRs --, two
+        // changed nothing, and neither did s_setprio 1 for the blend waves: profiles/adam_overlap_ab.txt)
+        if (adam >= 0) { sgr_sh_adam_zero_wave<4>(job, adam * 64); return; }
+    }
     if (SGR_FORWARD_INVALID(header, list_cap)) return;  // the forward was a no-op (blk_nb, masks, lists are not there)
     __shared__ float2 s_zw[BW_SUB * BW_ZW_STRIDE];
-    const int wg = blockIdx.x;
     int slot, sub;
     sgr_slot_of_workgroup(wg, slot, sub);
     if (slot >= T_tiles) return;
@@ -1200,8 +1226,8 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
 #else
 #define SGR_BWD_OCC
 #endif
-__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_w(SGR_BWD_PARAMS) { blend_bwd_body<false>(SGR_BWD_ARGS); }
-__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_wx(SGR_BWD_PARAMS) { blend_bwd_body<true>(SGR_BWD_ARGS); }  // exact alpha (SGR_BWD_HEAD_X)
+__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_w(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<false>(SGR_BWD_ARGS, job); }
+__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_wx(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<true>(SGR_BWD_ARGS, job); }  // exact alpha (SGR_BWD_HEAD_X)
 
 // Launch order of the backward: tiles by how deep the forward walked them (tile_maxc), deepest first, so that the waves still
 // running when the grid drains are the short ones.  (Workgroups start in index order; with ~2.5 dispatch rounds of waves whose
@@ -1229,11 +1255,11 @@ void sgr_launch_blend_fwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
                           const GeomRec* rec, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_maxc,
                           uint32_t* tile_walked, float* out_color, unsigned long long* blk_mask, uint32_t* blk_nb,
                           uint32_t* header, uint32_t list_cap, const uint32_t* tile_need, const uint32_t* launch_order, hipStream_t s,
-                          uint32_t* repair_flag, uint32_t* repair_list, int exact, uint32_t deep_min)
+                          uint32_t* repair_flag, uint32_t* repair_list, int exact, uint32_t deep_min, uint8_t* reach)
 {
     const int T = gx * gy;  // (tile_maxc and tile_walked were zeroed by the tile scan: the blocks of a tile combine with atomicMax)
     hipLaunchKernelGGL(exact ? k_blend_fwd_wx : k_blend_fwd_w, dim3(sgr_blend_grid(T)), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, rec, bg, final_T,
-                       n_contrib, tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, list_cap, tile_need, launch_order,
+                       n_contrib, tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, list_cap, reach, tile_need, launch_order,
                        tile_need ? repair_flag : nullptr, repair_list, tile_need ? deep_min : 0u);
 }
 
@@ -1274,13 +1300,13 @@ void sgr_launch_blend_fwd_deep(int W, int H, int gx, int gy, const uint32_t* til
 void sgr_launch_blend_fwd_repair(int W, int H, int gx, int gy, const uint32_t* tile_start, const uint32_t* point_list,
                                  const GeomRec* rec, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_maxc,
                                  uint32_t* tile_walked, float* out_color, unsigned long long* blk_mask, uint32_t* blk_nb,
-                                 uint32_t* header, uint32_t list_cap, const uint32_t* repair_list, hipStream_t s, int exact)
+                                 uint32_t* header, uint32_t list_cap, const uint32_t* repair_list, hipStream_t s, int exact, uint8_t* reach)
 {
     const int T = gx * gy;
     const int cover = T < SGR_REPAIR_TILES ? T : SGR_REPAIR_TILES;
     // (T_tiles stays the tile count: it clamps the list's entries; the slots beyond the listed tiles leave at once)
     hipLaunchKernelGGL(exact ? k_blend_fwd_repairx : k_blend_fwd_repair, dim3(sgr_blend_grid(cover)), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, rec, bg,
-                       final_T, n_contrib, tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, list_cap, repair_list);
+                       final_T, n_contrib, tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, list_cap, reach, repair_list);
 }
 
 // behind the blend: this view's launch order (for its backward: order_scratch; for the camera's next forward: order_out), the walk
@@ -1305,15 +1331,28 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
                           const char* binning, const uint32_t* blk_nb, const GeomRec* rec, const float* bg,
                           const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, float* acc,
                           const uint32_t* tile_maxc, const uint32_t* header, uint32_t list_cap, uint32_t* tile_order, int order_ready,
-                          hipStream_t s, int exact)
+                          hipStream_t s, int exact, const SgrShAdamJob* job_in)
 {
     const int T = gx * gy;
+    SgrShAdamJob job = {};
+    unsigned grid = sgr_blend_grid(T);
+#ifndef SGR_SLOT_RUNS
+    if (job_in && job_in->P > 0 && job_in->k >= 8 && (job_in->k & 7) == 0) {
+        job = *job_in;
+        const int n_adam = (job.P + 63) / 64;
+        job.n_groups = (int)(grid / 32u);
+        job.n_with = n_adam / job.k < job.n_groups ? n_adam / job.k : job.n_groups;
+        grid += (unsigned)n_adam;
+    }
+#endif
     if (order_ready) {}                           // (the forward sorted: sgr_forward_opts.tile_order_out)
     else if (4 * T < 8192) tile_order = nullptr;  // (fewer waves than the chip holds at once: nothing to order)
     else {
-        SgrTileOrderJob job = {T, list_cap, tile_maxc, nullptr, header, tile_order, nullptr, nullptr, nullptr, 0.f, gx, gy};
-        hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, job);
+        SgrTileOrderJob order_job = {T, list_cap, tile_maxc, nullptr, header, tile_order, nullptr, nullptr, nullptr, 0.f, gx, gy};
+        hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, order_job);
     }
-    hipLaunchKernelGGL(exact ? k_blend_bwd_wx : k_blend_bwd_w, dim3(sgr_blend_grid(T)), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, binning, blk_nb, rec,
-                       bg, final_T, n_contrib, dL_dpix, acc, tile_order, header, list_cap);
+    hipLaunchKernelGGL(exact ? k_blend_bwd_wx : k_blend_bwd_w, dim3(grid), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, binning, blk_nb, rec,
+                       bg, final_T, n_contrib, dL_dpix, acc, tile_order, header, list_cap, job);
+    // (a job this launch could not carry -- k no multiple of 8, a build with other slot runs -- is still done: a launch of its own)
+    if (job_in && job_in->P > 0 && job.P == 0) sgr_launch_sh_adam_zero(*job_in, s);
 }

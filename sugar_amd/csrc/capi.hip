@@ -137,9 +137,27 @@ uint32_t sgr_deep_min()
     return (uint32_t)g_deep_min;
 }
 
+// SH-Adam of unreached Gaussians inside the blend backward's launch (include/sugar_raster.h: sgr_set_adam_overlap); SGR_ADAM_OVERLAP
+// in the environment sets the default, SGR_ADAM_OVERLAP_K the Adam workgroups behind every 32 blend workgroups (a multiple of 8)
+static int g_adam_overlap = -1;
+int sgr_adam_overlap()
+{
+    if (g_adam_overlap < 0) { const char* e = getenv("SGR_ADAM_OVERLAP"); g_adam_overlap = e ? (e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0)) : SGR_ADAM_OVERLAP_DEFAULT; }
+    return g_adam_overlap;
+}
+int sgr_adam_overlap_k()
+{
+    static int k = -1;
+    if (k < 0) { const char* e = getenv("SGR_ADAM_OVERLAP_K"); k = e ? atoi(e) : 24; if (k < 8 || (k & 7)) k = 24; }
+    return k;
+}
+
 extern "C" {
 
 int sgr_abi_version(void) { return SGR_ABI_VERSION; }
+void sgr_set_adam_overlap(int on) { g_adam_overlap = on == 2 ? 2 : (on ? 1 : 0); }
+int sgr_get_adam_overlap(void) { return sgr_adam_overlap(); }
+size_t sgr_geom_reach_offset_bytes(int P) { return sgr_geom_reach_offset(P); }
 void sgr_set_deep_min(int entries) { g_deep_min = entries > 0 ? entries : 0; }
 int sgr_get_deep_min(void) { return (int)sgr_deep_min(); }
 void sgr_set_exact_alpha(int on) { g_exact_alpha = on ? 1 : 0; }
@@ -239,6 +257,8 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
     uint32_t* repair_flag = reinterpret_cast<uint32_t*>(img + IL.repair_flag);
     uint32_t* repair_list = reinterpret_cast<uint32_t*>(img + IL.repair_list);
 
+    // reach flags for a caller that splits SH-Adam by them (sgr_trainer_step): set by every blend kernel of this forward
+    uint8_t* reach = (flags & SGR_FLAG_REACH) ? reinterpret_cast<uint8_t*>(geom + sgr_geom_reach_offset(P)) : nullptr;
     uint32_t* blk_hist = reinterpret_cast<uint32_t*>(img + IL.blk_hist);
     char* sort_scratch = geom + sgr_geom_sort_offset(P);
     const int per_block = legacy_ok ? (((P + IL.n_blocks - 1) / IL.n_blocks + 63) / 64) * 64 : 0;  // Gaussians per slice
@@ -357,7 +377,9 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
             // Long lists: the blocks of tiles whose hinted list exceeds deep_min go to the eight-wave kernel on the side stream, beside
             // the one-wave kernel (which skips exactly those).  Only with a walk hint: without one every tile's full list counts.
             const uint32_t deep_cfg = sgr_deep_min();
-            SideStream* dside = (deep_cfg && opts->tile_need && two_level && !debug && !(flags & SGR_FLAG_NO_DEEP)) ? side_stream() : nullptr;
+            // (not in a forward that sets reach flags: the eight-wave kernel does not flag -- the pointer cost it a wave per SIMD -- so such
+            // a forward blends every block with the one-wave kernel; sgr_trainer_step leaves the flags off for a view that asks for deep lists)
+            SideStream* dside = (deep_cfg && opts->tile_need && two_level && !debug && !(flags & SGR_FLAG_NO_DEEP) && !reach) ? side_stream() : nullptr;
             const uint32_t deep_min = dside ? deep_cfg : 0u;
             if (dside) {
                 sgr_launch_deep_list(IL.gx, IL.gy, tile_start, opts->tile_need, deep_min, header, (uint32_t)R_,
@@ -372,7 +394,7 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
             }
             sgr_launch_blend_fwd(width, height, IL.gx, IL.gy, tile_start, point_list, rec, background, final_T, n_contrib,
                                  tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, (uint32_t)R_, opts->tile_need,
-                                 opts->tile_order, s, hint_repair ? repair_flag : nullptr, repair_list, exact, deep_min);
+                                 opts->tile_order, s, hint_repair ? repair_flag : nullptr, repair_list, exact, deep_min, reach);
             if (dside) HIP_TRY(hipStreamWaitEvent(s, dside->join, 0));
         }   // (that stage timer -- bench.py's roofline.launch_ms -- brackets k_blend_fwd_w alone; the two gated launches are a stage of their own)
         {
@@ -385,7 +407,7 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
                 sgr_launch_bin2_write(IL.gx, IL.gy, B2, bin2, header + 4, n_chunks_, rects, order, tile_start, point_list,
                                       nosync_ ? (uint32_t)R_ : 0xFFFFFFFFu, repair_flag, s, header + SGR_HDR_REPAIR, 512u);
                 sgr_launch_blend_fwd_repair(width, height, IL.gx, IL.gy, tile_start, point_list, rec, background, final_T, n_contrib,
-                                            tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, (uint32_t)R_, repair_list, s, exact);
+                                            tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, (uint32_t)R_, repair_list, s, exact, reach);
             }
         }
         if (flags & SGR_FLAG_DEFER_POST) {  // (the caller's next kernel carries the post-blend job: sgr_forward_post_job)
@@ -516,7 +538,8 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
                          const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, char* geom_buffer,
                          char* binning_buffer, char* img_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
                          float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                         float* dL_dscale, float* dL_drot, int debug, void* stream, const sgr_backward_opts* opts = nullptr)
+                         float* dL_dscale, float* dL_drot, int debug, void* stream, const sgr_backward_opts* opts = nullptr,
+                         const SgrShAdamJob* job = nullptr)
 {
     hipStream_t s = (hipStream_t)stream;
     const int raw_params = (phase & SGR_MODE_RAW_PARAMS) ? 1 : 0;
@@ -561,7 +584,9 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
                                  reinterpret_cast<const uint32_t*>(img_buffer + IL.header), (uint32_t)(R > 0xFFFFFFFFll ? 0xFFFFFFFFll : R),
                                  reinterpret_cast<uint32_t*>(img_buffer + IL.tile_cursor),
                                  (opts && (opts->flags & SGR_BWD_TILE_ORDER_READY)) ? 1 : 0, s,
-                                 (sgr_exact_alpha() || (opts && (opts->flags & SGR_BWD_EXACT_ALPHA))) ? 1 : 0);
+                                 (sgr_exact_alpha() || (opts && (opts->flags & SGR_BWD_EXACT_ALPHA))) ? 1 : 0, job);
+        } else if (job) {
+            sgr_launch_sh_adam_zero(*job, s);  // (no blend backward to ride in)
         }
         STAGE_CHECK("blend_bwd");
         if (phase == 1) {
@@ -695,6 +720,53 @@ int sgr_sh_adam_from_views_ex(int P, int n_views, int D, int M, const float* mea
     return 0;
 }
 
+// the two halves of SH-Adam split by reach flag (csrc/sh_adam_update.h)
+static bool sh_split_ok(int M, const float* sh, const float* m, const float* v)
+{
+    return M == 16 && ((((uintptr_t)sh | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+}
+
+int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                          float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
+                          uint32_t guard_capacity, void* stream)
+{
+    if (P <= 0) return 0;
+    if (step < 1 || !sh_params || !exp_avg || !exp_avg_sq || !reach) return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad: bad argument");
+    if (!sh_split_ok(M, sh_params, exp_avg, exp_avg_sq))
+        return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad: needs M == 16 and 16-byte aligned buffers");
+    SgrShAdamJob job = {};
+    job.P = P; job.sh = sh_params; job.exp_avg = exp_avg; job.exp_avg_sq = exp_avg_sq; job.reach = reach;
+    job.lr_dc = lr_dc; job.lr_rest = lr_rest; job.b1 = beta1; job.b2 = beta2; job.omb1 = sgr_one_minus(beta1); job.omb2 = sgr_one_minus(beta2);
+    job.eps = eps; job.grad_scale = grad_scale; job.zero = 0.f; job.guard = guard_header; job.guard_cap = guard_capacity;
+    sgr_bias_corrections(beta1, beta2, step, &job.bc1, &job.bc2_sqrt);
+    sgr_launch_sh_adam_zero(job, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_zero_grad: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
+                                  const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq,
+                                  float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                                  uint8_t* reach, const uint32_t* guard_header, uint32_t guard_capacity, void* stream)
+{
+    if (P <= 0) return 0;
+    if (n_views <= 0 || D < 0 || D > 3 || M < (D + 1) * (D + 1) || step < 1 || !means3D || !campos_all || !dcolor_all || !sh_params ||
+        !exp_avg || !exp_avg_sq || !reach)
+        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: bad argument");
+    if (view_stride != 0 && view_stride < P) return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: view_stride < P");
+    if (!sh_split_ok(M, sh_params, exp_avg, exp_avg_sq))
+        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: needs M == 16 and 16-byte aligned buffers");
+    float bc1, bc2_sqrt;
+    sgr_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
+    sgr_launch_sh_adam_from_views(P, n_views, D, M, (size_t)(view_stride ? view_stride : P), means3D, campos_all, dcolor_all, sh_params, exp_avg,
+                                  exp_avg_sq, lr_dc, lr_rest, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, nullptr, (hipStream_t)stream,
+                                  guard_header, guard_capacity, reach);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_from_views_masked: ") + hipGetErrorString(e));
+    return 0;
+}
+
 int sgr_sh_adam_from_views(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
                            const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq, float lr_dc,
                            float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, void* stream)
@@ -704,3 +776,16 @@ int sgr_sh_adam_from_views(int P, int n_views, int D, int M, const float* means3
 }
 
 }  // extern "C"
+
+// sgr_backward_ex for sgr_trainer_step (train.hip): compact SH mode on raw parameters, with the zero-gradient SH-Adam job for the
+// blend backward's launch (sgr_common.h)
+int sgr_backward_job(int phase, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
+                     const float* shs, const float* scales, const float* rotations, const float* viewmatrix, const float* projmatrix,
+                     const float* cam_pos, float tan_fovx, float tan_fovy, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                     const float* dL_dpix, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dscale,
+                     float* dL_drot, void* stream, const sgr_backward_opts* opts, const SgrShAdamJob* job)
+{
+    return backward_impl(phase, P, D, M, R, background, width, height, means3D, shs, nullptr, scales, 1.0f, rotations, nullptr, viewmatrix,
+                         projmatrix, cam_pos, tan_fovx, tan_fovy, geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, nullptr,
+                         dL_dopacity, dL_dcolor, dL_dmean3D, nullptr, nullptr, dL_dscale, dL_drot, 0, stream, opts, job);
+}

@@ -18,6 +18,7 @@
 // instead of being stored (24 B/Gaussian of HBM traffic each way for ~40 flops).
 #include "../../include/sugar_raster.h"
 #include "sgr_common.h"
+#include "sh_adam_update.h"
 
 namespace {
 
@@ -1004,6 +1005,7 @@ __global__ void __launch_bounds__(256) k_sh_grad_from_views(int P, int V, int D,
 struct ShAdamArgs {
     float lr_dc, lr_rest, b1, b2, omb1, omb2, eps, bc1, bc2_sqrt, grad_scale;
     const uint32_t* guard; uint32_t guard_cap;  // forward header + list capacity: the step is a no-op if that forward was invalid (NULL: no check)
+    uint8_t* reach;  // MASKED: the reach flags (sh_adam_update.h)
 };
 
 // One wave per 64 Gaussians.  Phase 1: lane = Gaussian, the 48 sums in registers, dropped into an LDS panel (row stride 52
@@ -1014,7 +1016,12 @@ struct ShAdamArgs {
 // DIR (dmean_extra != NULL, M == 16): phase 1 also loads the Gaussian's 48 coefficients (the wave's 12 KB block, which
 // phase 2 then streams out of the cache) and writes the view-direction part of dL/dmean3D, summed over the views, to
 // dmean_extra[P][3]; the flat Adam kernel adds it to the position gradient (sgr_adam_step_ex).
-template <bool DIR>
+// MASKED (M == 16, aligned buffers, no DIR): only the rows whose reach flag is set are updated -- the others got their zero-gradient
+// step from sgr_sh_adam_zero_wave --, and the wave puts its 64 flags back to 0 (it is their last reader, as k_preprocess_bwd is the
+// accumulator table's).  Unflagged rows run no phase 1 and load no colour, and phase 2 walks the flagged rows only: their lane
+// numbers are compacted into an LDS list, and the stream is n_flagged x 12 float4 instead of 64 x 12 (a fifth of the steps on the
+// metric scene; clamped addresses as below, not lane-predicated loads).
+template <bool DIR, bool MASKED = false>
 __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, int M, size_t vstride,
                                                            const float* __restrict__ means3D,
                                                            const float* __restrict__ campos, const float* __restrict__ dcolor,
@@ -1027,6 +1034,11 @@ __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, 
     const int lane = threadIdx.x;
     const int g0 = blockIdx.x * 64;
     const int idx = g0 + lane;
+    unsigned long long flagged = ~0ull;  // MASKED: bit g <=> row g0 + g is updated here
+    if (MASKED) {
+        flagged = __ballot(idx < P && a.reach[min(idx, P - 1)] != 0);
+        if (flagged == 0ull) return;
+    }
     float4 pkeep[12];  // DIR: the wave's 64 x 48 coefficients in the streaming layout of phase 2 (read from memory once)
     if (DIR) {
         // coalesced into the panel (row = Gaussian) for the direction term, and kept in registers for the Adam update
@@ -1055,7 +1067,7 @@ __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, 
     }
     {
         float acc[48];
-        if (idx < P) {
+        if (idx < P && ((flagged >> lane) & 1ull)) {
             sh_grad_sum_over_views(idx, vstride, V, D, means3D, campos, dcolor, acc);
         } else {
 #pragma unroll
@@ -1070,14 +1082,51 @@ __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, 
     const int n_sh = 3 * M;
     const int live = min(64, P - g0);
     auto upd = [&](int c, float g, float& p, float& m, float& v) {
-        g *= a.grad_scale;
-        m = a.b1 * m + a.omb1 * g;
-        v = a.b2 * v + a.omb2 * g * g;
-        const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-        p -= ((c < 3 ? a.lr_dc : a.lr_rest) / a.bc1) * (m / denom);
+        sh_adam_update(g, p, m, v, c < 3 ? a.lr_dc : a.lr_rest, a.grad_scale, a.b1, a.b2, a.omb1, a.omb2, a.eps, a.bc1, a.bc2_sqrt);
     };
     const size_t base = (size_t)g0 * n_sh;
-    if (n_sh == 48 && ((((uintptr_t)sh | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0)) {
+    if (MASKED) {  // (n_sh == 48 and aligned buffers: the launcher's callers have checked)
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        __shared__ int s_row[64];  // the flagged rows of the wave, in order
+        const int n4f = 12 * __popcll(flagged);
+        if ((flagged >> lane) & 1ull)
+            s_row[__builtin_amdgcn_mbcnt_hi((uint32_t)(flagged >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)flagged, 0u))] = lane;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        f4* p4 = reinterpret_cast<f4*>(sh + base);
+        f4* m4 = reinterpret_cast<f4*>(exp_avg + base);
+        f4* v4 = reinterpret_cast<f4*>(exp_avg_sq + base);
+        constexpr int NB = 4;
+#pragma clang loop unroll(disable)
+        for (int st0 = 0; st0 * 64 < n4f; st0 += NB) {
+            f4 pv[NB], mv[NB], vv[NB];
+            int ee[NB];
+#pragma unroll
+            for (int u = 0; u < NB; u++) {
+                const int j = min((st0 + u) * 64 + lane, n4f - 1);  // float4 index inside the compacted stream
+                const int r = j / 12;
+                ee[u] = s_row[r] * 12 + (j - r * 12);                // ... and inside the wave's 64 x 48 block
+                pv[u] = p4[ee[u]];
+                mv[u] = __builtin_nontemporal_load(&m4[ee[u]]); vv[u] = __builtin_nontemporal_load(&v4[ee[u]]);
+            }
+#pragma unroll
+            for (int u = 0; u < NB; u++) {
+                if ((st0 + u) * 64 + lane < n4f) {
+                    const int e4 = ee[u], g = e4 / 12, c4 = e4 - g * 12;
+                    const float4 gr = *reinterpret_cast<const float4*>(s_g + g * SHA_STRIDE + 4 * c4);
+                    float p[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, m[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
+                    float v[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+                    const float gq[4] = {gr.x, gr.y, gr.z, gr.w};
+#pragma unroll
+                    for (int k = 0; k < 4; k++) upd(4 * c4 + k, gq[k], p[k], m[k], v[k]);
+                    const f4 po = {p[0], p[1], p[2], p[3]}, mo = {m[0], m[1], m[2], m[3]}, vo = {v[0], v[1], v[2], v[3]};
+                    p4[e4] = po;
+                    __builtin_nontemporal_store(mo, &m4[e4]);
+                    __builtin_nontemporal_store(vo, &v4[e4]);
+                }
+            }
+        }
+    } else if (n_sh == 48 && ((((uintptr_t)sh | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0)) {
         typedef float f4 __attribute__((ext_vector_type(4)));
         f4* p4 = reinterpret_cast<f4*>(sh + base);
         f4* m4 = reinterpret_cast<f4*>(exp_avg + base);
@@ -1125,7 +1174,11 @@ __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, 
             sh[base + e] = p; exp_avg[base + e] = m; exp_avg_sq[base + e] = v;
         }
     }
+    if (MASKED && idx < P) a.reach[idx] = 0;
 }
+
+// the zero-gradient half as a launch of its own: one wave per 64 Gaussians (the same body rides in k_blend_bwd_w / _wx)
+__global__ void __launch_bounds__(64) k_sh_adam_zero(SgrShAdamJob job) { sgr_sh_adam_zero_wave<4>(job, (int)blockIdx.x * 64); }
 
 // ---------------------------------------------------------------------------------------------
 // SuGaR.get_points_rgb (sugar_scene/sugar_model.py:839-883): colours = clamp_min(eval_sh(levels-1, sh, dir) + 0.5, 0) with
@@ -1273,15 +1326,24 @@ void sgr_launch_masked_colors(int P, const GeomRec* rec, const float* acc, float
 void sgr_launch_sh_adam_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,
                                    const float* dcolor, float* sh, float* exp_avg, float* exp_avg_sq, float lr_dc, float lr_rest, float b1, float b2,
                                    float eps, float bc1, float bc2_sqrt, float grad_scale, float* dmean_extra, hipStream_t s,
-                                   const uint32_t* guard, uint32_t guard_cap)
+                                   const uint32_t* guard, uint32_t guard_cap, uint8_t* reach)
 {
-    ShAdamArgs a = {lr_dc, lr_rest, b1, b2, sgr_one_minus(b1), sgr_one_minus(b2), eps, bc1, bc2_sqrt, grad_scale, guard, guard_cap};
-    if (dmean_extra)
+    ShAdamArgs a = {lr_dc, lr_rest, b1, b2, sgr_one_minus(b1), sgr_one_minus(b2), eps, bc1, bc2_sqrt, grad_scale, guard, guard_cap, reach};
+    if (reach)  // (the callers have checked: M == 16, aligned buffers, no dmean_extra)
+        hipLaunchKernelGGL((k_sh_adam_from_views<false, true>), dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos,
+                           dcolor, sh, exp_avg, exp_avg_sq, a, dmean_extra);
+    else if (dmean_extra)
         hipLaunchKernelGGL(k_sh_adam_from_views<true>, dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos, dcolor,
                            sh, exp_avg, exp_avg_sq, a, dmean_extra);
     else
         hipLaunchKernelGGL(k_sh_adam_from_views<false>, dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos, dcolor,
                            sh, exp_avg, exp_avg_sq, a, dmean_extra);
+}
+
+void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s)
+{
+    if (job.P <= 0) return;
+    hipLaunchKernelGGL(k_sh_adam_zero, dim3((job.P + 63) / 64), dim3(64), 0, s, job);
 }
 
 void sgr_launch_sh_grad_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,

@@ -16,7 +16,7 @@
 #define SGR_BIN_SLICES 1024          // slices of the depth order in the ordered binning (one T-entry LDS histogram each)
 
 // ---- private scratch layouts -----------------------------------------------------------------
-// geom  : [ GeomRec rec[P] | acc f32[P][16] | sort scratch ]   48 B / Gaussian record (AoS: one gather = 1-2 lines),
+// geom  : [ GeomRec rec[P] | acc f32[P][16] | sort scratch | reach u8[P] ]   48 B / Gaussian record (AoS: one gather = 1-2 lines),
 //           the backward's per-Gaussian accumulator (zeroed by each backward, or kept zero between backwards: SGR_BWD_ACC_CLEAN), and the depth sort's ping-pong
 //           key/value arrays (the sorted Gaussian order stays there for the backward-free forward only)
 // img   : [ final_T f32[WH] | n_contrib u32[WH] | tile_start u32[T+1] | tile_count u32[T] |
@@ -44,7 +44,10 @@ static inline size_t sgr_geom_sort_offset(int P) { return sgr_geom_acc_offset(P)
 size_t sgr_sort_rects_offset(int P);    // binning.hip: offset of the packed rectangles inside the sort scratch
 // reset of the backward's accumulator table inside a geometry scratch (capi.hip; timed as SGR_STAGE_FILL): hipSuccess or the error
 hipError_t sgr_acc_reset(char* geom_buffer, int P, hipStream_t s);
-static inline size_t sgr_geom_total(int P) { return sgr_geom_sort_offset(P) + sgr_sort_scratch_bytes(P); }
+// reach flags: one byte per Gaussian behind the sort scratch, != 0 <=> a forward blend gave the Gaussian a survivor bit in some block
+// since the masked SH-Adam last cleared it (a superset of what this view's blend backward can reach; see sh_adam_update.h)
+static inline size_t sgr_geom_reach_offset(int P) { return sgr_geom_sort_offset(P) + sgr_align(sgr_sort_scratch_bytes(P)); }
+static inline size_t sgr_geom_total(int P) { return sgr_geom_reach_offset(P) + sgr_align((size_t)(P > 0 ? P : 1)); }
 
 struct ImgLayout {
     size_t final_T, n_contrib, tile_start, tile_cursor, tile_maxc, tile_walked, blk_nb, header, repair_flag, repair_list, deep_list, blk_hist, total;
@@ -202,10 +205,28 @@ static inline void sgr_bias_corrections(float beta1, float beta2, int step, floa
     *bc2_sqrt = (float)sqrt(1.0 - pow(sgr_intended_double(beta2), (double)step));
 }
 
+// reach (M == 16, 16-byte aligned buffers only): the masked mode -- rows whose reach flag is 0 are left alone, the flags are cleared
 void sgr_launch_sh_adam_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,
                                    const float* dcolor, float* sh, float* exp_avg, float* exp_avg_sq, float lr_dc, float lr_rest, float b1, float b2,
                                    float eps, float bc1, float bc2_sqrt, float grad_scale, float* dmean_extra, hipStream_t s,
-                                   const uint32_t* guard = nullptr, uint32_t guard_cap = 0);
+                                   const uint32_t* guard = nullptr, uint32_t guard_cap = 0, uint8_t* reach = nullptr);
+// The other half of the masked mode: the Adam update with a gradient of zero for the rows whose reach flag is 0 (sh_adam_update.h).
+// As a job it rides in the blend backward's launch as extra workgroups (sgr_launch_blend_bwd); sgr_launch_sh_adam_zero is the same
+// body as a launch of its own.
+struct SgrShAdamJob {
+    int P;                       // Gaussians; 0 = no job
+    int k;                       // Adam workgroups behind every group of 32 blend workgroups (a multiple of 8)
+    int n_groups, n_with;        // set by sgr_launch_blend_bwd: groups of 32 blend workgroups, and how many of them carry k Adam workgroups
+    float* sh; float* exp_avg; float* exp_avg_sq;   // [P][48], 16-byte aligned
+    const uint8_t* reach;        // [P]
+    float lr_dc, lr_rest, b1, b2, omb1, omb2, eps, bc1, bc2_sqrt, grad_scale;
+    float zero;                  // 0.f, opaque to the compiler: the gradient
+    const uint32_t* guard; uint32_t guard_cap;  // as ShAdamArgs: forward header + list capacity (NULL: no check)
+};
+void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s);
+#define SGR_ADAM_OVERLAP_DEFAULT 1
+int sgr_adam_overlap();   // capi.hip: process-wide switch (sgr_set_adam_overlap)
+int sgr_adam_overlap_k(); // capi.hip: SgrShAdamJob.k (SGR_ADAM_OVERLAP_K in the environment)
 // sgr_adam_step_ex with the same guard (adam.hip)
 int sgr_adam_launch(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,
                     const long long* seg_begin, const long long* seg_end, const float* seg_lr_a, const float* seg_lr_b,
@@ -234,7 +255,8 @@ void sgr_launch_blend_fwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
                           const GeomRec* rec, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_maxc,
                           uint32_t* tile_walked, float* out_color, unsigned long long* blk_mask, uint32_t* blk_nb,
                           uint32_t* header, uint32_t list_cap, const uint32_t* tile_need, const uint32_t* launch_order, hipStream_t s,
-                          uint32_t* repair_flag = nullptr, uint32_t* repair_list = nullptr, int exact = 0, uint32_t deep_min = 0u);
+                          uint32_t* repair_flag = nullptr, uint32_t* repair_list = nullptr, int exact = 0, uint32_t deep_min = 0u,
+                          uint8_t* reach = nullptr);  // reach: [P] reach flags to set (sgr_geom_reach_offset), or NULL
 // blocks of tiles whose hinted list is longer than deep_min entries: eight waves per block (blend.hip); deep_list: [T] words of scratch
 void sgr_launch_deep_list(int gx, int gy, const uint32_t* tile_start, const uint32_t* tile_need, uint32_t deep_min, uint32_t* header,
                           uint32_t list_cap, uint32_t* deep_list, hipStream_t s);
@@ -252,7 +274,8 @@ uint32_t sgr_deep_min();   // capi.hip: process-wide threshold of the eight-wave
 void sgr_launch_blend_fwd_repair(int W, int H, int gx, int gy, const uint32_t* tile_start, const uint32_t* point_list,
                                  const GeomRec* rec, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_maxc,
                                  uint32_t* tile_walked, float* out_color, unsigned long long* blk_mask, uint32_t* blk_nb,
-                                 uint32_t* header, uint32_t list_cap, const uint32_t* repair_list, hipStream_t s, int exact = 0);
+                                 uint32_t* header, uint32_t list_cap, const uint32_t* repair_list, hipStream_t s, int exact = 0,
+                                 uint8_t* reach = nullptr);
 void sgr_launch_blend_fwd_post(int gx, int gy, const uint32_t* tile_maxc, const uint32_t* tile_walked, uint32_t* header, uint32_t list_cap,
                                uint32_t* tile_need_out, float hint_margin, uint32_t* header_host_dev, uint32_t* order_scratch,
                                uint32_t* order_out, hipStream_t s);
@@ -261,7 +284,13 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
                           const char* binning, const uint32_t* blk_nb, const GeomRec* rec, const float* bg,
                           const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, float* acc,
                           const uint32_t* tile_maxc, const uint32_t* header, uint32_t list_cap, uint32_t* tile_order, int order_ready,
-                          hipStream_t s, int exact = 0);
+                          hipStream_t s, int exact = 0, const SgrShAdamJob* job = nullptr);
+// sgr_backward_ex with a zero-gradient SH-Adam job for the blend backward's launch (capi.hip; train.hip is the caller)
+int sgr_backward_job(int phase, int P, int D, int M, int64_t R, const float* background, int width, int height, const float* means3D,
+                     const float* shs, const float* scales, const float* rotations, const float* viewmatrix, const float* projmatrix,
+                     const float* cam_pos, float tan_fovx, float tan_fovy, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                     const float* dL_dpix, float* dL_dmean2D, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dscale,
+                     float* dL_drot, void* stream, const sgr_backward_opts* opts, const SgrShAdamJob* job);
 // the post-blend bookkeeping as a job another kernel can carry (tile_order.h); capi.hip fills it for a forward that was run with
 // SGR_FLAG_DEFER_POST, loss.hip's forward kernel executes it in a spare workgroup
 struct SgrTileOrderJob;

@@ -121,6 +121,10 @@ sgr_trainer* sgr_trainer_create(const sgr_train_config* cfg)
     const float lr[4] = {c.lr_xyz, c.lr_opacity, c.lr_scaling, c.lr_rotation};
     for (int k = 0; k < 4; k++) { t->seg_begin[k] = b[k]; t->seg_end[k] = b[k] + n[k]; t->seg_lr[k] = lr[k]; t->seg_one[k] = 1; }
     std::memset(c.header_host, 0, 64);
+    // the reach flags start from zero (a stale 1 is safe, a stale 0 is not: sh_adam_update.h); a new topology is a new trainer
+    if (hipMemset(c.geom + sgr_geom_reach_offset(c.P), 0, (size_t)c.P) != hipSuccess) {
+        (void)hipEventDestroy(t->hdr_event); delete t; g_train_err = "sgr_trainer_create: clearing the reach flags failed"; return nullptr;
+    }
     {
         // (pinned memory that is not mapped into the device's address space: the forward copies the header with copy commands and
         // does its own bookkeeping; SGR_TRAINER_NO_DEFER forces that path for a test)
@@ -174,13 +178,27 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
     const float* rot = flat + c.off_rotation;
     const uint32_t* header = reinterpret_cast<const uint32_t*>(c.img + sgr_img_header_offset(W, H));
     const uint32_t cap = (uint32_t)(c.binning_capacity > 0xFFFFFFFFll ? 0xFFFFFFFFll : c.binning_capacity);
+    // SGR_BWD_DENSE in the environment: the verification switch of the backward preprocess (every rendered row read) for the whole step
+    const char* dense_env = getenv("SGR_BWD_DENSE");
+    const bool bwd_dense = dense_env && dense_env[0] && dense_env[0] != '0';
+    // SH-Adam split by reach flag (sh_adam_update.h): only for a whole step on this rank's one view -- a Gaussian unreached here may be
+    // reached in another rank's view --, M == 16, a preprocess that takes its zero-row exit, and a view that does not ask for the
+    // eight-wave blend kernel (which does not flag).  overlap == 2: the forward flags, the
+    // dense kernel runs and nothing clears them (verification of the flags).
+    const int overlap = sgr_adam_overlap();
+    const bool reach_ok = overlap != 0 && phases == 15 && !(v->flags & SGR_VIEW_DEEP_LISTS) && ex && ex->n_views == 1 && !ex->all_colors && !ex->all_campos &&
+                          !(ex->g_end > ex->g_begin) && c.M == 16 && !bwd_dense &&
+                          ((((uintptr_t)(flat + c.off_features) | (uintptr_t)(c.exp_avg + c.off_features) |
+                             (uintptr_t)(c.exp_avg_sq + c.off_features)) & 15) == 0);
+    const bool split = reach_ok && overlap == 1;
+    uint8_t* reach = reinterpret_cast<uint8_t*>(c.geom + sgr_geom_reach_offset(P));
     if (phases & 1) {
         if (!v->viewmatrix || !v->projmatrix || !v->campos || !v->gt_image) return tfail(SGR_E_INVALID, "sgr_trainer_step: null view");
         FixedBuf g = {c.geom, c.geom_bytes, 0}, b = {c.binning, c.binning_bytes, 0}, i = {c.img, c.img_bytes, 0};
         sgr_forward_opts fo;
         std::memset(&fo, 0, sizeof(fo));
         fo.binning_capacity = c.binning_capacity;
-        fo.flags = SGR_FLAG_RAW_PARAMS | ((v->flags & SGR_VIEW_DEEP_LISTS) ? 0 : SGR_FLAG_NO_DEEP);
+        fo.flags = SGR_FLAG_RAW_PARAMS | ((v->flags & SGR_VIEW_DEEP_LISTS) ? 0 : SGR_FLAG_NO_DEEP) | (reach_ok ? SGR_FLAG_REACH : 0);
         fo.header_host = c.header_host;
         // the post-blend bookkeeping (launch order, walk hint, second header copy) rides in the loss forward kernel, which is what
         // follows the blend here; the event for the host is recorded behind it
@@ -215,7 +233,20 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
         // (SGR_BWD_ACC_CLEAN: the accumulator table is zero between steps -- the preprocess kernel puts the few records the blend
         // backward dirtied back -- so no step resets its 64 B per Gaussian; see acc_dirty below)
         sgr_backward_opts bo = {c.max_radii2D, c.grad_accum, c.denom, c.colors + 3 * (size_t)P,
-                                ((t->defer_post || v->tile_order_out) ? SGR_BWD_TILE_ORDER_READY : 0) | SGR_BWD_ACC_CLEAN};
+                                ((t->defer_post || v->tile_order_out) ? SGR_BWD_TILE_ORDER_READY : 0) | SGR_BWD_ACC_CLEAN |
+                                    (bwd_dense ? SGR_BWD_DENSE : 0)};
+        // the zero-gradient half of SH-Adam rides in the blend backward's launch (the bias corrections of ex->step are known here)
+        SgrShAdamJob job = {};
+        if (split) {
+            if (ex->step < 1) return tfail(SGR_E_INVALID, "sgr_trainer_step: exchange description missing");
+            job.P = P; job.k = sgr_adam_overlap_k();
+            job.sh = flat + c.off_features; job.exp_avg = c.exp_avg + c.off_features; job.exp_avg_sq = c.exp_avg_sq + c.off_features;
+            job.reach = reach;
+            job.lr_dc = c.lr_features_dc; job.lr_rest = c.lr_features_rest; job.b1 = c.beta1; job.b2 = c.beta2;
+            job.omb1 = sgr_one_minus(c.beta1); job.omb2 = sgr_one_minus(c.beta2); job.eps = c.eps; job.grad_scale = ex->grad_scale;
+            job.zero = 0.f; job.guard = header; job.guard_cap = cap;
+            sgr_bias_corrections(c.beta1, c.beta2, ex->step, &job.bc1, &job.bc2_sqrt);
+        }
         // compact SH mode (dL_dsh == NULL), raw-parameter gradients straight into the flat gradient buffer.  Both halves asked
         // for at once (no collective to start in between): ONE pass, the preprocess kernel writes the masked colour gradients
         // itself (the split costs a 23 us kernel of its own)
@@ -229,11 +260,10 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
                     return tfail(SGR_E_HIP, "sgr_trainer_step: accumulator reset failed");
                 t->acc_dirty = true;
             }
-            const int rc = sgr_backward_ex(ph | SGR_MODE_RAW_PARAMS, P, c.D, c.M, t->R, c.background, W, H, means3D, shs, nullptr, scal,
-                                           1.0f, rot, nullptr, v->viewmatrix, v->projmatrix, v->campos, v->tan_fovx, v->tan_fovy,
-                                           c.radii, c.geom, c.binning, c.img, c.grad_image, c.dL_dmean2D, nullptr,
-                                           grad + c.off_opacity, c.colors, grad + c.off_xyz, nullptr, nullptr, grad + c.off_scaling,
-                                           grad + c.off_rotation, 0, stream, &bo);
+            const int rc = sgr_backward_job(ph | SGR_MODE_RAW_PARAMS, P, c.D, c.M, t->R, c.background, W, H, means3D, shs, scal, rot,
+                                            v->viewmatrix, v->projmatrix, v->campos, v->tan_fovx, v->tan_fovy, c.geom, c.binning, c.img,
+                                            c.grad_image, c.dL_dmean2D, grad + c.off_opacity, c.colors, grad + c.off_xyz,
+                                            grad + c.off_scaling, grad + c.off_rotation, stream, &bo, split ? &job : nullptr);
             if (rc < 0) return tfail(rc, std::string("backward: ") + sgr_last_error());
             if (ph != 1) t->acc_dirty = false;
         }
@@ -257,7 +287,7 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
             sgr_launch_sh_adam_from_views((int)(g1 - g0), ex->n_views, c.D, c.M, stride, means3D + 3 * (size_t)g0, cams, cols,
                                           flat + c.off_features + fo, c.exp_avg + c.off_features + fo, c.exp_avg_sq + c.off_features + fo,
                                           c.lr_features_dc, c.lr_features_rest, c.beta1, c.beta2, c.eps, bc1, bc2_sqrt, ex->grad_scale, nullptr, s,
-                                          header, cap);
+                                          header, cap, split ? reach : nullptr);  // (split: the flagged rows only; clears the flags)
             tm.stop();
             if (hipGetLastError() != hipSuccess) return tfail(SGR_E_HIP, "sh_adam launch failed");
         }
