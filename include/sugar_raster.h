@@ -268,6 +268,21 @@ typedef struct sgr_backward_opts {
  * reader) stores zeros over every record it found non-zero, so the promise holds again afterwards.  For callers that keep one
  * geometry scratch across steps (sgr_trainer does; it resets the table itself once, and again after a step that failed half-way). */
 #define SGR_BWD_ACC_CLEAN 4
+/* Rows by reach flag (a backward without dL_dsh; phases 0 and 2; not with SGR_BWD_DENSE: SGR_E_INVALID otherwise).  The caller PROMISES
+ * the superset invariant of SGR_FLAG_REACH: the reach flag at sgr_geom_reach_offset_bytes(P) is set for every Gaussian whose nine sums
+ * in the accumulator table are not all zero.  The backward preprocess then loads neither the record nor the accumulator record of an
+ * unflagged Gaussian, and keeps a second byte table at sgr_geom_rowdirty_offset_bytes(P) of the geometry scratch: rowdirty[i] == 1 means
+ * that row i of this call's output buffers may hold non-zeros from the last call that wrote it.  A flagged Gaussian goes the usual way,
+ * and its byte becomes 1 if it took the full backward and 0 if its row was written as zeros; an unflagged one gets its row written as
+ * zeros (every output of the call, dL_dcolor and dL_dmean2D included) and its byte cleared if the byte was 1, and NO store otherwise.
+ * After the call every output row holds what the call without the bit leaves there, PROVIDED that on entry every row whose byte is 0
+ * held +0 in every output.  That holds for a caller that passes the same output buffers and geometry scratch to every call and lets
+ * nothing else write them; whenever it may not hold -- the first call, other buffers, a call without the bit in between -- or-ing in
+ * SGR_BWD_ROWS_UNKNOWN makes this one call treat every row as dirty (and rewrite the whole table).  The densification statistics of an
+ * unflagged Gaussian are updated as before (its radius is the one word of its record that is read, and only when they are asked for).
+ * Neither bit changes the reach flags.  sgr_trainer_step sets the bits itself (sgr_set_rows_by_reach). */
+#define SGR_BWD_ROWS_BY_REACH 16
+#define SGR_BWD_ROWS_UNKNOWN 32
 int sgr_backward_ex(int phase, int P, int D, int M, int64_t R,
                     const float* background, int width, int height,
                     const float* means3D, const float* shs, const float* colors_precomp,
@@ -328,6 +343,15 @@ int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float*
 void sgr_set_adam_overlap(int on);
 int sgr_get_adam_overlap(void);
 size_t sgr_geom_reach_offset_bytes(int P);
+/* Process-wide switch of the same train step (on by default; SGR_ROWS_BY_REACH=0 / 1 in the environment sets the default): where the
+ * SH-Adam split runs, the backward preprocess runs with SGR_BWD_ROWS_BY_REACH over the trainer's flat gradient buffer, its colour
+ * buffer and, if given, dL_dmean2D.  The trainer passes SGR_BWD_ROWS_UNKNOWN on its first such step and after every step that wrote
+ * the rows another way (phase-by-phase calls, the exchange, SGR_BWD_DENSE, sgr_set_adam_overlap(0 or 2), a deep-list view, M != 16, an
+ * error return).  Between two steps nothing but the trainer may write non-zeros into those buffers (or: sgr_trainer_invalidate_rows).  0 = every row is loaded and
+ * written in every step.  rowdirty[P]: one byte per Gaussian, read and written by the backward preprocess alone. */
+void sgr_set_rows_by_reach(int on);
+int sgr_get_rows_by_reach(void);
+size_t sgr_geom_rowdirty_offset_bytes(int P);
 
 /* Rasterizer::markVisible, DGR/cuda_rasterizer/rasterizer.h:24-29 / rasterizer_impl.cu:141-153.
  * present[P] is one byte per Gaussian (bool). */
@@ -519,6 +543,9 @@ const char* sgr_trainer_last_error(void);
  * that returned an error between the blend backward and the backward preprocess), 0 if the table is known to be zero
  * (SGR_BWD_ACC_CLEAN: the preprocess kernel of the last step put it back). */
 int sgr_trainer_acc_dirty(sgr_trainer* t);
+/* sgr_set_rows_by_reach: for a caller that DID let something else write the flat gradient buffer, the colour buffer or dL_dmean2D since this trainer's last
+ * step (another trainer over the same buffers, autograd, a collective): the next step by reach flag treats every row as dirty. */
+void sgr_trainer_invalidate_rows(sgr_trainer* t);
 /* The gradient exchange of the view-sharded step INSIDE the library (extension; SURVEY.md section 8e: one view per GPU, replicas,
  * "RCCL all-reduce of parameter grads over xGMI"): RCCL is bound at run time (dlopen of librccl.so -- the copy PyTorch has already
  * loaded, if any), one communicator per trainer, collectives on a stream of the library's own.

@@ -57,6 +57,10 @@ SIGNATURES = {
     "sgr_set_adam_overlap": (None, [_i]),
     "sgr_get_adam_overlap": (_i, []),
     "sgr_geom_reach_offset_bytes": (_sz, [_i]),
+    "sgr_set_rows_by_reach": (None, [_i]),
+    "sgr_trainer_invalidate_rows": (None, [_vp]),
+    "sgr_get_rows_by_reach": (_i, []),
+    "sgr_geom_rowdirty_offset_bytes": (_sz, [_i]),
     "sgr_geom_bytes": (_sz, [_i]),
     "sgr_img_bytes": (_sz, [_i, _i]),
     "sgr_binning_bytes": (_sz, [_i64, _i, _i]),
@@ -216,6 +220,7 @@ class TrainExchange(C.Structure):
 
 SGR_FLAG_RAW_PARAMS, SGR_FLAG_SINGLE_LEVEL_BINNING, SGR_FLAG_SPECULATIVE = 1, 2, 8
 SGR_BWD_TILE_ORDER_READY, SGR_BWD_ACC_CLEAN, SGR_BWD_DENSE = 1, 4, 8
+SGR_BWD_ROWS_BY_REACH, SGR_BWD_ROWS_UNKNOWN = 16, 32
 HDR_R, HDR_HINT_MISS, HDR_L1_OVERFLOW = 0, 3, 6
 
 _lib = None

@@ -151,10 +151,21 @@ int sgr_adam_overlap_k()
     if (k < 0) { const char* e = getenv("SGR_ADAM_OVERLAP_K"); k = e ? atoi(e) : 24; if (k < 8 || (k & 7)) k = 24; }
     return k;
 }
+// Backward preprocess of the train step by reach flag (include/sugar_raster.h: sgr_set_rows_by_reach); SGR_ROWS_BY_REACH=0 / 1 in the
+// environment sets the default (on)
+static int g_rows_by_reach = -1;
+int sgr_rows_by_reach()
+{
+    if (g_rows_by_reach < 0) { const char* e = getenv("SGR_ROWS_BY_REACH"); g_rows_by_reach = (e && e[0] == '0') ? 0 : 1; }
+    return g_rows_by_reach;
+}
 
 extern "C" {
 
 int sgr_abi_version(void) { return SGR_ABI_VERSION; }
+void sgr_set_rows_by_reach(int on) { g_rows_by_reach = on ? 1 : 0; }
+int sgr_get_rows_by_reach(void) { return sgr_rows_by_reach(); }
+size_t sgr_geom_rowdirty_offset_bytes(int P) { return sgr_geom_rowdirty_offset(P); }
 void sgr_set_adam_overlap(int on) { g_adam_overlap = on == 2 ? 2 : (on ? 1 : 0); }
 int sgr_get_adam_overlap(void) { return sgr_adam_overlap(); }
 size_t sgr_geom_reach_offset_bytes(int P) { return sgr_geom_reach_offset(P); }
@@ -574,6 +585,10 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
     // SGR_BWD_ACC_CLEAN: the caller promises that the table is all zero on entry (no reset), and the preprocess kernel -- its last
     // reader in phases 0 and 2 -- stores zeros over every record it found non-zero.  (In phase 1 k_masked_colors is not the last reader.)
     const bool acc_clean = opts && (opts->flags & SGR_BWD_ACC_CLEAN);
+    // SGR_BWD_ROWS_BY_REACH: the preprocess half trusts the reach flags (phase 1 runs no preprocess half and ignores the bit)
+    const bool by_reach = opts && (opts->flags & SGR_BWD_ROWS_BY_REACH) && phase != 1;
+    if (by_reach && (dL_dsh || (opts->flags & SGR_BWD_DENSE)))
+        return fail(SGR_E_INVALID, "SGR_BWD_ROWS_BY_REACH is for a backward without dL_dsh and excludes SGR_BWD_DENSE");
     if (phase != 2) {
         if (!acc_clean) HIP_TRY(sgr_acc_reset(geom_buffer, P, s));
         if (R > 0) {
@@ -610,6 +625,9 @@ static int backward_impl(int phase, int P, int D, int M, int64_t R, const float*
     pb.acc = acc;
     pb.acc_clean = acc_clean ? 1 : 0;
     pb.dense = (opts && (opts->flags & SGR_BWD_DENSE)) ? 1 : 0;
+    pb.reach = by_reach ? reinterpret_cast<const uint8_t*>(geom_buffer + sgr_geom_reach_offset(P)) : nullptr;
+    pb.rowdirty = by_reach ? reinterpret_cast<uint8_t*>(geom_buffer + sgr_geom_rowdirty_offset(P)) : nullptr;
+    pb.rows_unknown = (by_reach && (opts->flags & SGR_BWD_ROWS_UNKNOWN)) ? 1 : 0;
     pb.header = reinterpret_cast<const uint32_t*>(img_buffer + IL.header);
     pb.list_cap = (uint32_t)(R > 0xFFFFFFFFll ? 0xFFFFFFFFll : R);
     pb.campos_row = (opts && compact && phase == 0) ? opts->campos_row : nullptr;  // (phase 1 wrote it with the colours)

@@ -508,6 +508,12 @@ __device__ __forceinline__ void bwd_acc_clean(const PreprocessBwdArgs& a, int id
     ap[0] = z4; ap[1] = z4;
     a.acc[SGR_ACC_STRIDE * (size_t)idx + 8] = 0.f;
 }
+// The densification statistics of a rendered row whose gradients are zero (grad_accum += |0| is no store)
+__device__ __forceinline__ void bwd_zero_row_stats(const PreprocessBwdArgs& a, int idx, int radius)
+{
+    if (a.dens_denom) a.dens_denom[idx] += 1.0f;
+    if (a.dens_max_radii) a.dens_max_radii[idx] = fmaxf(a.dens_max_radii[idx], (float)radius);
+}
 // Every output row of Gaussian idx as zeros.  `stats`: the row was rendered (radius > 0) and the blend backward left it untouched --
 // the densification statistics count it as the full path would (denom += 1, max_radii2D = max(., radius), grad_accum += |0| is no
 // store); a culled Gaussian or an invalid forward leaves them alone.
@@ -534,9 +540,23 @@ __device__ __forceinline__ void bwd_zero_row(const PreprocessBwdArgs& a, int idx
     }
     if (a.dL_dscale) { a.dL_dscale[i3] = 0; a.dL_dscale[i3 + 1] = 0; a.dL_dscale[i3 + 2] = 0; }
     if (a.dL_drot) { float4 z = {0, 0, 0, 0}; *reinterpret_cast<float4*>(a.dL_drot + 4 * (size_t)idx) = z; }
-    if (stats) {
-        if (a.dens_denom) a.dens_denom[idx] += 1.0f;
-        if (a.dens_max_radii) a.dens_max_radii[idx] = fmaxf(a.dens_max_radii[idx], (float)radius);
+    if (stats) bwd_zero_row_stats(a, idx, radius);
+}
+
+// SGR_BWD_ROWS_BY_REACH, a Gaussian whose reach flag is 0: the blend backward cannot have reached it, so its nine sums are zero (the
+// accumulator table is clean between backwards) and its row is the zero row -- without the record and the accumulator record being
+// loaded, and without a store where the row holds zeros already (`row_dirty` == false).  The densification statistics still count a
+// rendered row: the radius is the one word of the record they need (the same int the dense path takes from rec1.w).
+__device__ __forceinline__ void bwd_unreached_row(const PreprocessBwdArgs& a, int idx, bool row_dirty, bool fwd_invalid)
+{
+    int radius = 0;
+    if ((a.dens_denom || a.dens_max_radii) && !fwd_invalid) radius = a.rec[idx].radius;
+    const bool rendered = radius > 0;
+    if (row_dirty) {
+        bwd_zero_row<false>(a, idx, nullptr, rendered, radius);
+        a.rowdirty[idx] = 0;
+    } else if (rendered) {
+        bwd_zero_row_stats(a, idx, radius);
     }
 }
 
@@ -799,8 +819,11 @@ __device__ __forceinline__ void bwd_full_row(const PreprocessBwdArgs& a, const i
 // camera, the header) is requested in one batch; then the row goes one of three ways: zeros without statistics (culled, or the
 // forward was invalid), zeros with statistics (rendered, but the blend backward never reached it: most of a frustum is occluded in
 // any one view), or the full backward.  a.dense (SGR_BWD_DENSE) sends every rendered row through the full backward.
+// With a.reach (SGR_BWD_ROWS_BY_REACH, compact mode) a lane whose Gaussian is not flagged requests nothing but its two flag bytes.
+// The body is shared with k_preprocess_bwd_packed, which hands it the rows of an LDS list (`consecutive` == false).
 template <bool STORE_SH, int SH>
-__device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, float* __restrict__ stage, const int idx0)
+__device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, float* __restrict__ stage, const int idx0,
+                                                    const bool consecutive = true)  // (wave-uniform) lane l holds the Gaussian behind lane l - 1's
 {
     if (a.campos_row && idx0 < 3) a.campos_row[idx0] = a.cam_pos[idx0];  // (see sgr_backward_opts)
     // a sync-free forward whose list outgrew its capacity (or missed its walk hint) did not happen: the gradients are written as
@@ -811,9 +834,27 @@ __device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, 
     if (a.header) { hdr_r = a.header[SGR_HDR_R]; hdr_miss = a.header[SGR_HDR_HINT_MISS]; hdr_ovf = a.header[4 + SGR_B2_HDR_OVERFLOW]; }
     const bool valid = idx0 < a.P;
     const int idx = valid ? idx0 : a.P - 1;  // lanes past the end re-read the last Gaussian and store nothing
+    // SGR_BWD_ROWS_BY_REACH (compact mode): the two flag bytes decide whether this lane loads anything else
+    const bool by_reach = !STORE_SH && a.reach != nullptr;
+    bool reached = true, row_dirty = true;
+    if (by_reach) {
+        const uint8_t f = a.reach[idx], d = a.rowdirty[idx];
+        reached = valid && f != 0;
+        row_dirty = a.rows_unknown || d != 0;
+        if (!__any(reached)) {  // (wave-uniform) nothing to clean, no camera, no record
+            if (valid) bwd_unreached_row(a, idx, row_dirty, hdr_r > a.list_cap || hdr_miss != 0u || hdr_ovf != 0u);
+            return;
+        }
+    }
     const float cam_raw = cam_request(a.viewmatrix, a.projmatrix, a.cam_pos);
     BwdHead h;
-    bwd_head_load(a, idx, h);
+    if (by_reach) {  // an unreached lane keeps zero sums: it takes no part in the cleaning below
+        const float4 z4 = {0.f, 0.f, 0.f, 0.f};
+        h.rec0 = z4; h.rec1 = z4; h.rec2 = z4; h.s0 = z4; h.s1 = z4; h.s2x = 0.f;
+        if (reached) bwd_head_load(a, idx, h);
+    } else {
+        bwd_head_load(a, idx, h);
+    }
     Cam cam;
     cam_unpack(cam_raw, cam);
     if (a.acc_clean) {
@@ -823,7 +864,7 @@ __device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, 
         // instead (every lane's record has been read by now: the ballot below waits for all of them).
         const bool dirty = valid && bwd_touched(h.s0, h.s1, h.s2x);
         const unsigned long long m = __ballot(dirty);
-        if (__popcll(m) >= 32) {  // (wave-uniform)
+        if (consecutive && __popcll(m) >= 32) {  // (wave-uniform)
             const int lane = threadIdx.x & 63;
             const long long row0 = (long long)idx0 - lane;  // the wave's first Gaussian
             float4* w4 = reinterpret_cast<float4*>(a.acc + SGR_ACC_STRIDE * (size_t)row0);
@@ -839,10 +880,17 @@ __device__ __forceinline__ void preprocess_bwd_lane(const PreprocessBwdArgs& a, 
     }
     if (!valid) return;
     const bool fwd_invalid = hdr_r > a.list_cap || hdr_miss != 0u || hdr_ovf != 0u;  // SGR_FORWARD_INVALID: zero gradients, no statistics
+    if (by_reach && !reached) {
+        bwd_unreached_row(a, idx, row_dirty, fwd_invalid);
+        return;
+    }
     const int radius = __float_as_int(h.rec1.w);
     const bool touched = bwd_touched(h.s0, h.s1, h.s2x);
     const bool rendered = !fwd_invalid && radius > 0;
-    if (!rendered || !(touched || a.dense)) {
+    const bool full = rendered && (touched || a.dense);
+    // (the table says what the row holds after this launch; stored only where that changes, or where the table itself is not known)
+    if (by_reach && (a.rows_unknown || row_dirty != full)) a.rowdirty[idx] = full ? 1 : 0;
+    if (!full) {
         bwd_zero_row<STORE_SH>(a, idx, stage, rendered, radius);
         return;
     }
@@ -877,6 +925,65 @@ __global__ void __launch_bounds__(256, SGR_PRE_BWD_BLOCKS) k_preprocess_bwd(Prep
             }
         }
     }
+}
+
+// SGR_BWD_ROWS_BY_REACH: the reached rows of a workgroup packed into dense waves.  With a tenth of the Gaussians reached, a lane
+// per Gaussian runs the full backward -- a chain of dependent round trips through a long body -- in nearly every wave for about six
+// live lanes.  Here the workgroup's first wave reads the 256 reach and row-dirty bytes as words, writes the zero rows that are owed,
+// and compacts the indices of the reached Gaussians into an LDS list with ballots; the lane body above then runs over that list:
+// about 26 rows in one wave on the metric scene, the other three waves leave.  A workgroup that finds three quarters of its Gaussians
+// reached (a bound, opaque surface: 99 %) skips the list and takes its rows in order, as k_preprocess_bwd does -- that keeps the
+// accumulator's wave-wide cleaning.  The same body runs either way, once per thread and without a loop (256 K Gaussians per workgroup
+// with a loop over the list, K = 2, 4, 8, cost 185 VGPRs and a wave per SIMD for 2 us of the kernel and nothing of the step:
+// profiles/rows_by_reach_ab.txt), so every output is bit-identical to the lane kernel's.
+template <int SH>
+__global__ void __launch_bounds__(256, SGR_PRE_BWD_BLOCKS) k_preprocess_bwd_packed(PreprocessBwdArgs a)
+{
+    __shared__ int s_list[256];
+    __shared__ int s_n;  // rows listed, or -1: the rows in order
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long long base = (long long)blockIdx.x * 256;
+    const int rows = (int)min(256ll, (long long)a.P - base);
+    if (a.campos_row && blockIdx.x == 0 && tid < 3) a.campos_row[tid] = a.cam_pos[tid];
+    if (tid < 64) {
+        // one word of four flag bytes per lane (the tables are padded to 256 bytes: a word that starts below P lies inside them)
+        uint32_t rw = 0u, dw = 0u;
+        if (4 * lane < rows) {
+            rw = *reinterpret_cast<const uint32_t*>(a.reach + base + 4 * lane);
+            dw = *reinterpret_cast<const uint32_t*>(a.rowdirty + base + 4 * lane);
+            const int live = rows - 4 * lane;  // (bytes at and beyond P are padding)
+            if (live < 4) { const uint32_t keep = (1u << (8 * live)) - 1u; rw &= keep; dw &= keep; }
+        }
+        unsigned long long m[4];
+        int n_reached = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { m[j] = __ballot(((rw >> (8 * j)) & 0xFFu) != 0u); n_reached += __popcll(m[j]); }
+        // (wave-uniform.  Also in order where every unreached row has work of its own -- the densification statistics, or a launch
+        // that rewrites every row: that is a lane each, not four rows per lane of this one wave)
+        const bool in_order = 4 * n_reached >= 3 * rows || a.dens_denom || a.dens_max_radii || a.rows_unknown;
+        if (!in_order) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            int at = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int g = (int)base + 4 * lane + j;
+                if ((rw >> (8 * j)) & 0xFFu) {
+                    s_list[at + __popcll(m[j] & below)] = g;
+                } else if (((dw >> (8 * j)) & 0xFFu) != 0u) {  // (an unreached row that owes its zeros; no statistics here)
+                    bwd_unreached_row(a, g, true, false);
+                }
+                at += __popcll(m[j]);
+            }
+        }
+        if (lane == 0) s_n = in_order ? -1 : n_reached;
+    }
+    __syncthreads();
+    const int listed = s_n;
+    const bool in_order = listed < 0;
+    const int n = in_order ? rows : listed;
+    if ((tid & ~63) >= n) return;  // (whole waves: the body below ballots)
+    const int idx0 = in_order ? (int)base + tid : (tid < n ? s_list[tid] : a.P);  // (at or beyond P: the lane stores nothing)
+    preprocess_bwd_lane<false, SH>(a, nullptr, idx0, in_order);
 }
 
 // dL/dsh[k][c] = sum over views v of  basis_k(dir_v) * g_v[c]   with dir_v = normalize(mean - campos_v) and g_v the
@@ -1306,6 +1413,12 @@ void sgr_launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
     if (a.P <= 0) return;
     const dim3 grid((a.P + 255) / 256);
     const int mode = (!a.shs || a.sh_dir_elsewhere) ? 2 : (sh_fast_layout(a.shs, a.M) ? 0 : 1);
+    if (a.reach && !a.dL_dsh) {  // SGR_BWD_ROWS_BY_REACH
+        if (mode == 0) hipLaunchKernelGGL((k_preprocess_bwd_packed<0>), grid, dim3(256), 0, s, a);
+        else if (mode == 1) hipLaunchKernelGGL((k_preprocess_bwd_packed<1>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_preprocess_bwd_packed<2>), grid, dim3(256), 0, s, a);
+        return;
+    }
     if (a.dL_dsh) {
         if (mode == 0) hipLaunchKernelGGL((k_preprocess_bwd<true, 0>), grid, dim3(256), 0, s, a);
         else if (mode == 1) hipLaunchKernelGGL((k_preprocess_bwd<true, 1>), grid, dim3(256), 0, s, a);

@@ -16,7 +16,7 @@
 #define SGR_BIN_SLICES 1024          // slices of the depth order in the ordered binning (one T-entry LDS histogram each)
 
 // ---- private scratch layouts -----------------------------------------------------------------
-// geom  : [ GeomRec rec[P] | acc f32[P][16] | sort scratch | reach u8[P] ]   48 B / Gaussian record (AoS: one gather = 1-2 lines),
+// geom  : [ GeomRec rec[P] | acc f32[P][16] | sort scratch | reach u8[P] | rowdirty u8[P] ]   48 B / Gaussian record (AoS: one gather = 1-2 lines),
 //           the backward's per-Gaussian accumulator (zeroed by each backward, or kept zero between backwards: SGR_BWD_ACC_CLEAN), and the depth sort's ping-pong
 //           key/value arrays (the sorted Gaussian order stays there for the backward-free forward only)
 // img   : [ final_T f32[WH] | n_contrib u32[WH] | tile_start u32[T+1] | tile_count u32[T] |
@@ -47,7 +47,10 @@ hipError_t sgr_acc_reset(char* geom_buffer, int P, hipStream_t s);
 // reach flags: one byte per Gaussian behind the sort scratch, != 0 <=> a forward blend gave the Gaussian a survivor bit in some block
 // since the masked SH-Adam last cleared it (a superset of what this view's blend backward can reach; see sh_adam_update.h)
 static inline size_t sgr_geom_reach_offset(int P) { return sgr_geom_sort_offset(P) + sgr_align(sgr_sort_scratch_bytes(P)); }
-static inline size_t sgr_geom_total(int P) { return sgr_geom_reach_offset(P) + sgr_align((size_t)(P > 0 ? P : 1)); }
+// row-dirty table: one byte per Gaussian behind the reach flags, 1 <=> row i of the backward's output buffers may hold non-zeros from
+// the last backward that wrote it (SGR_BWD_ROWS_BY_REACH; only k_preprocess_bwd reads or writes it)
+static inline size_t sgr_geom_rowdirty_offset(int P) { return sgr_geom_reach_offset(P) + sgr_align((size_t)(P > 0 ? P : 1)); }
+static inline size_t sgr_geom_total(int P) { return sgr_geom_rowdirty_offset(P) + sgr_align((size_t)(P > 0 ? P : 1)); }
 
 struct ImgLayout {
     size_t final_T, n_contrib, tile_start, tile_cursor, tile_maxc, tile_walked, blk_nb, header, repair_flag, repair_list, deep_list, blk_hist, total;
@@ -172,6 +175,11 @@ struct PreprocessBwdArgs {
     float* acc;  // [P][SGR_ACC_STRIDE] sums from the blend backward: {dcol r,g,b, S0, Sx, Sy, Sxx, Sxy, Syy, pad x3}
     int acc_clean;  // SGR_BWD_ACC_CLEAN: store zeros over every record found non-zero, after reading it (this kernel is its last reader)
     int dense;      // SGR_BWD_DENSE: every rendered row takes the full backward (no zero-row exit)
+    // SGR_BWD_ROWS_BY_REACH (compact mode only, both NULL otherwise): a Gaussian whose reach flag is 0 has zero sums by the superset
+    // invariant -- neither its record nor its accumulator record is loaded, and its output row is stored to (as zeros) only if
+    // rowdirty says that it may hold something else
+    const uint8_t* reach; uint8_t* rowdirty;
+    int rows_unknown;  // SGR_BWD_ROWS_UNKNOWN: the output buffers do not match rowdirty -- every row counts as dirty for this launch
     float* dL_dmean2D; float* dL_dconic; float* dL_dopacity; float* dL_dcolor;  // written here from acc
     float* dL_dmean3D; float* dL_dcov3D; float* dL_dsh; float* dL_dscale; float* dL_drot;
 };
@@ -226,6 +234,7 @@ struct SgrShAdamJob {
 void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s);
 #define SGR_ADAM_OVERLAP_DEFAULT 1
 int sgr_adam_overlap();   // capi.hip: process-wide switch (sgr_set_adam_overlap)
+int sgr_rows_by_reach();  // capi.hip: process-wide switch (sgr_set_rows_by_reach)
 int sgr_adam_overlap_k(); // capi.hip: SgrShAdamJob.k (SGR_ADAM_OVERLAP_K in the environment)
 // sgr_adam_step_ex with the same guard (adam.hip)
 int sgr_adam_launch(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,

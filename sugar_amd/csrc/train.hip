@@ -84,6 +84,8 @@ struct sgr_trainer {
     hipEvent_t hdr_event = nullptr;
     bool have_forward = false;
     bool acc_dirty = true;      // the geometry scratch's accumulator table may hold non-zero records: the next backward resets it
+    bool rows_unknown = true;   // the step's output rows (flat gradient, masked colours) may not match the geometry scratch's row-dirty
+                                // table: the next backward by reach flag treats every row as dirty (SGR_BWD_ROWS_UNKNOWN)
     bool defer_post = false;    // the post-blend bookkeeping rides in the loss forward kernel (needs a device-mapped header_host)
     int64_t R = 0;              // what the last forward returned (= the capacity)
     long long seg_begin[4], seg_end[4];
@@ -121,8 +123,9 @@ sgr_trainer* sgr_trainer_create(const sgr_train_config* cfg)
     const float lr[4] = {c.lr_xyz, c.lr_opacity, c.lr_scaling, c.lr_rotation};
     for (int k = 0; k < 4; k++) { t->seg_begin[k] = b[k]; t->seg_end[k] = b[k] + n[k]; t->seg_lr[k] = lr[k]; t->seg_one[k] = 1; }
     std::memset(c.header_host, 0, 64);
-    // the reach flags start from zero (a stale 1 is safe, a stale 0 is not: sh_adam_update.h); a new topology is a new trainer
-    if (hipMemset(c.geom + sgr_geom_reach_offset(c.P), 0, (size_t)c.P) != hipSuccess) {
+    // the reach flags start from zero (a stale 1 is safe, a stale 0 is not: sh_adam_update.h); a new topology is a new trainer.  The
+    // row-dirty table behind them is cleared in the same stroke (rows_unknown holds until the first step by reach flag anyway)
+    if (hipMemset(c.geom + sgr_geom_reach_offset(c.P), 0, sgr_geom_rowdirty_offset(c.P) + (size_t)c.P - sgr_geom_reach_offset(c.P)) != hipSuccess) {
         (void)hipEventDestroy(t->hdr_event); delete t; g_train_err = "sgr_trainer_create: clearing the reach flags failed"; return nullptr;
     }
     {
@@ -152,6 +155,7 @@ int sgr_trainer_set_binning(sgr_trainer* t, char* binning, size_t bytes, int64_t
 }
 
 int sgr_trainer_acc_dirty(sgr_trainer* t) { return (t && !t->acc_dirty) ? 0 : 1; }
+void sgr_trainer_invalidate_rows(sgr_trainer* t) { if (t) t->rows_unknown = true; }
 
 int sgr_trainer_forward_valid(sgr_trainer* t, uint32_t* header_out)
 {
@@ -191,6 +195,8 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
                           ((((uintptr_t)(flat + c.off_features) | (uintptr_t)(c.exp_avg + c.off_features) |
                              (uintptr_t)(c.exp_avg_sq + c.off_features)) & 15) == 0);
     const bool split = reach_ok && overlap == 1;
+    // ... and the backward preprocess by the same flags: an unflagged Gaussian costs it two flag bytes (sgr_set_rows_by_reach)
+    const bool by_reach = split && sgr_rows_by_reach() != 0;
     uint8_t* reach = reinterpret_cast<uint8_t*>(c.geom + sgr_geom_reach_offset(P));
     if (phases & 1) {
         if (!v->viewmatrix || !v->projmatrix || !v->campos || !v->gt_image) return tfail(SGR_E_INVALID, "sgr_trainer_step: null view");
@@ -234,7 +240,11 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
         // backward dirtied back -- so no step resets its 64 B per Gaussian; see acc_dirty below)
         sgr_backward_opts bo = {c.max_radii2D, c.grad_accum, c.denom, c.colors + 3 * (size_t)P,
                                 ((t->defer_post || v->tile_order_out) ? SGR_BWD_TILE_ORDER_READY : 0) | SGR_BWD_ACC_CLEAN |
-                                    (bwd_dense ? SGR_BWD_DENSE : 0)};
+                                    (bwd_dense ? SGR_BWD_DENSE : 0) |
+                                    (by_reach ? (SGR_BWD_ROWS_BY_REACH | (t->rows_unknown ? SGR_BWD_ROWS_UNKNOWN : 0)) : 0)};
+        // every backward that writes the rows densely leaves them out of step with the row-dirty table, and so does one that returns
+        // an error half-way: the table counts again once a backward by reach flag has been enqueued
+        t->rows_unknown = true;
         // the zero-gradient half of SH-Adam rides in the blend backward's launch (the bias corrections of ex->step are known here)
         SgrShAdamJob job = {};
         if (split) {
@@ -266,6 +276,7 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
                                             grad + c.off_scaling, grad + c.off_rotation, stream, &bo, split ? &job : nullptr);
             if (rc < 0) return tfail(rc, std::string("backward: ") + sgr_last_error());
             if (ph != 1) t->acc_dirty = false;
+            if (by_reach) t->rows_unknown = false;
         }
     }
     if (phases & 12) {

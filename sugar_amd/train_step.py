@@ -677,6 +677,7 @@ class NativeTrainer:
             vp(self._img), self._img.numel(), vp(self._binning), self._binning.numel(), self.capacity, vp(self._loss_scratch),
             vp(self.image), vp(self._grad_image), vp(self.loss_out), vp(self._send), vp(self.radii), vp(self._hdr),
             st("viewspace_grad"), st("max_radii2D"), st("xyz_gradient_accum"), st("denom"))
+        self._rows_token, self._rows_stamp = object(), None   # (see _call)
         self._h = lib.sgr_trainer_create(C.byref(self._cfg))
         if not self._h:
             raise RuntimeError("sgr_trainer_create failed: " + lib.sgr_trainer_last_error().decode(errors="replace"))
@@ -775,6 +776,17 @@ class NativeTrainer:
         deep = 1 if (need is not None and ent5 is not None and ent5[5] > self._deep_min) else 0
         view = L.TrainView(cam.viewmatrix.data_ptr(), cam.projmatrix.data_ptr(), cam.campos.data_ptr(), cam.tanfovx, cam.tanfovy,
                            gt.data_ptr(), need, need_out, self.hint_margin, self._chunk_grid(key), order, order_out, deep)
+        if phases & 3:
+            # the backward by reach flag leaves alone the gradient rows it knows to hold zeros: tell the library when
+            # something else may have written them since this trainer's last step -- a torch operation on the buffers or on a view of
+            # them (a .grad of the parameters: autograd, zero_(), a collective) shows in their version counters, another native
+            # trainer over the same parameters in the owner mark
+            bufs = [self.params.flat_grad, self._send] + ([self.viewspace_grad] if self.densify_stats else [])
+            stamp = tuple(t._version for t in bufs)
+            if stamp != getattr(self, "_rows_stamp", None) or getattr(self.params, "_grad_rows_owner", None) is not self._rows_token:
+                self._lib.sgr_trainer_invalidate_rows(self._h)
+            self._rows_stamp = stamp
+            self.params._grad_rows_owner = self._rows_token
         with torch.cuda.device(self.dev):
             stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
             if exchange_step is not None:
