@@ -219,9 +219,10 @@ class TrainExchange(C.Structure):
 
 
 SGR_FLAG_RAW_PARAMS, SGR_FLAG_SINGLE_LEVEL_BINNING, SGR_FLAG_SPECULATIVE = 1, 2, 8
+SGR_FLAG_NO_DEEP, SGR_FLAG_REACH = 32, 64
 SGR_BWD_TILE_ORDER_READY, SGR_BWD_ACC_CLEAN, SGR_BWD_DENSE = 1, 4, 8
 SGR_BWD_ROWS_BY_REACH, SGR_BWD_ROWS_UNKNOWN = 16, 32
-HDR_R, HDR_HINT_MISS, HDR_L1_OVERFLOW = 0, 3, 6
+HDR_R, HDR_HINT_MISS, HDR_L1_OVERFLOW, HDR_REPAIR = 0, 3, 6, 7
 
 _lib = None
 

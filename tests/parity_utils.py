@@ -95,6 +95,34 @@ def run_hip(scene, cam, bg, *, use_sh=True, use_cov=False, sh_degree=3, scale_mo
     return out
 
 
+class _PatternScratch:
+    """diff_gaussian_rasterization._Scratch with every byte of the three buffers set to 0xFF (a NaN as a float, 2^32 - 1 as a count: whatever
+    a test reads back was written by a kernel) and the P reach flags, which a forward only ever SETS, cleared -- both on the current
+    stream, ahead of the forward's kernels"""
+
+    def __init__(self, device, reach_offset, P):
+        self.device, self.tensors, self._cbs, self.reach = device, {}, {}, (int(reach_offset), int(P))
+
+    def cb(self, name):
+        from sugar_amd import _lib
+
+        def alloc(_user, nbytes):
+            t = self.tensors[name] = torch.full((int(nbytes),), 0xFF, dtype=torch.uint8, device=self.device)
+            if name == "geom":
+                o, P = self.reach
+                assert o + P <= int(nbytes)
+                t[o:o + P] = 0
+            return t.data_ptr()
+
+        self._cbs[name] = _lib.ALLOC_FN(alloc)
+        return self._cbs[name]
+
+    def release(self):
+        t, self.tensors = self.tensors, {}
+        self._cbs.clear()
+        return t
+
+
 # float columns of the private 48-byte geometry record (GeomRec, sugar_amd/csrc/sgr_common.h)
 REC_XY, REC_CONIC, REC_OPACITY, REC_DEPTH, REC_RADIUS, REC_RGB, REC_CLAMPED = slice(0, 2), [2, 3, 4], 5, 6, 7, slice(8, 11), 11
 
@@ -122,9 +150,13 @@ class Run:
 
     raw: the raw 3DGS parameters (log scale, un-normalised quaternion, opacity logit), derived from the activated scene -- or, with
     raw_given, the scene's fields hold them already.  colors / cov: colors_precomp [P,3] / cov3D_precomp [P,6] instead of the SH
-    coefficients / of scales and rotations.  The image size is the camera's."""
+    coefficients / of scales and rotations.  The image size is the camera's.
+    flags: further SGR_FLAG_* bits of the forward; tile_need / tile_need_out: the walk hint going in / coming out (device uint32 per tile);
+    header_host: the forward's two header copies land in self.header (pinned, 16 words; read it after a synchronize).  With
+    SGR_FLAG_REACH the scratch starts as 0xFF bytes with the reach flags cleared (the forward only ever SETS them): see _PatternScratch."""
 
-    def __init__(self, scene, cam, bg, raw, *, raw_given=False, D=3, M=16, colors=None, cov=None, scale_modifier=1.0, device="cuda:0"):
+    def __init__(self, scene, cam, bg, raw, *, raw_given=False, D=3, M=16, colors=None, cov=None, scale_modifier=1.0, device="cuda:0",
+                 flags=0, tile_need=None, tile_need_out=None, header_host=False):
         from sugar_amd import _lib
         from sugar_amd.diff_gaussian_rasterization import _Scratch
         self.L, self.lib = _lib, _lib.load()
@@ -147,9 +179,12 @@ class Run:
         self.color = torch.empty(3, H, W, device=dev)
         self.radii = torch.empty(P, dtype=torch.int32, device=dev)
         self.dpix = torch.as_tensor(grad_image(W, H)).to(dev)
-        sc = _Scratch(dev)
-        opts = _lib.ForwardOpts(0, _lib.SGR_FLAG_RAW_PARAMS if raw else 0, None, None, None, None, 0.0, 0, None, None, None)
+        sc = _PatternScratch(dev, self.lib.sgr_geom_reach_offset_bytes(P), P) if flags & _lib.SGR_FLAG_REACH else _Scratch(dev)
+        self.header = torch.zeros(16, dtype=torch.int32).pin_memory() if header_host else None
+        self.tile_need, self.tile_need_out = tile_need, tile_need_out  # (kept alive)
         p = self.ptr
+        opts = _lib.ForwardOpts(0, (_lib.SGR_FLAG_RAW_PARAMS if raw else 0) | int(flags), p(self.header), None, p(tile_need), p(tile_need_out),
+                                0.0, 0, None, None, None)
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         self.R = self.lib.sgr_forward_ex(sc.cb("geom"), None, sc.cb("binning"), None, sc.cb("img"), None, P, self.D, self.M, p(self.bg),
                                          W, H, p(self.means), p(self.shs), p(self.colors), p(self.opac), p(self.scales), self.mod,
@@ -166,6 +201,43 @@ class Run:
         """the accumulator table float[P][16] inside the geometry scratch (a view: writable)"""
         o = self.lib.sgr_geom_acc_offset_bytes(self.P)
         return self.scratch["geom"][o:o + self.P * 64].view(torch.float32).view(self.P, 16)
+
+    def _img(self, offset_fn, n, dtype):
+        torch.cuda.synchronize()
+        o = offset_fn(self.W, self.H)
+        return self.scratch["img"][o:o + 4 * n].cpu().numpy().view(dtype)
+
+    @property
+    def tiles(self):
+        return ((self.W + 15) // 16) * ((self.H + 15) // 16)
+
+    def final_T(self):
+        return self._img(self.lib.sgr_img_final_T_offset, self.W * self.H, np.float32)
+
+    def n_contrib(self):
+        return self._img(self.lib.sgr_img_n_contrib_offset, self.W * self.H, np.uint32)
+
+    def tile_start(self):
+        return self._img(self.lib.sgr_img_tile_start_offset, self.tiles + 1, np.uint32)
+
+    def tile_maxc(self):
+        return self._img(self.lib.sgr_img_tile_maxc_offset, self.tiles, np.uint32)
+
+    def tile_walked(self):
+        """uint32[T]: the furthest list position any pixel of the tile examined"""
+        return self._img(self.lib.sgr_img_tile_walked_offset, self.tiles, np.uint32)
+
+    def point_list(self):
+        """the first tile_start[T] entries of the instance list: Gaussian ids, tile-major, depth order"""
+        n = int(self.tile_start()[-1])
+        o = self.lib.sgr_binning_point_list_offset(self.R)
+        return self.scratch["binning"][o:o + 4 * n].cpu().numpy().view(np.uint32)
+
+    def reach(self):
+        """the reach table, one byte per Gaussian (SGR_FLAG_REACH), on the host"""
+        torch.cuda.synchronize()
+        o = self.lib.sgr_geom_reach_offset_bytes(self.P)
+        return self.scratch["geom"][o:o + self.P].cpu().numpy()
 
     def record(self):
         """the forward's 48-byte record of every Gaussian, as float32 [P,12] on the host (columns: REC_* above)"""
