@@ -24,7 +24,7 @@ SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
     "binning.hip": ["-ffp-contract=off"],
     "binning2.hip": ["-ffp-contract=off"],
-    "blend.hip": ["-fno-slp-vectorize"] + os.environ.get("SGR_BLEND_DEFS", "").split(),  # the auto-formed v_pk_* pairs cost more v_mov shuffles than they save
+    "blend.hip": ["-fno-slp-vectorize"],  # the auto-formed v_pk_* pairs cost more v_mov shuffles than they save
     "knn.hip": ["-ffp-contract=off"],
     "mesh_raster.hip": ["-ffp-contract=off"],  # bit-exact with oracle/mesh_rasterizer.c
     "texture.hip": ["-ffp-contract=off"],      # the texel arithmetic of the reference's individually rounded tensor ops

@@ -90,7 +90,7 @@ __device__ __forceinline__ bool block_hit(float gxc, float gyc, float cx, float 
 //   out: live updated, n = entries not yet started when every lane had finished (0: the batch was walked to its end)
 // gfx950 hazards observed by hand (the compiler does not look inside): one independent instruction between v_exp_f32 and the
 // use of its result; EXEC is only ever written by SALU instructions before VALU instructions depend on it.
-#define SGR_FWD_BODY(X, Y, A, B, CZ, OP, R, G, BL, POS, XY, AB)                                     \
+#define SGR_FWD_BODY(X, Y, A, B, CZ, OP, R, G, BL, POS)                                             \
     "v_sub_f32 v60, " X ", %[px]\n"                                                                 \
     "v_sub_f32 v61, " Y ", %[py]\n"                                                                 \
     "v_mul_f32 v62, " B ", v61\n"                                                                   \
@@ -131,7 +131,10 @@ __device__ __forceinline__ bool block_hit(float gxc, float gyc, float cx, float 
 //   test_T = T (1 - alpha)
 // With it alpha, T, final_T and n_contrib are bit-identical to the reference's (compiled without contraction) and every gradient
 // tensor is within the reference's own run-to-run spread; 12 more VALU instructions per entry (33 against 21).
-#define SGR_FWD_BODY_X(X, Y, A, B, CZ, OP, R, G, BL, POS, XY, AB)                                   \
+// (Removed after c4def3b: the plain-C++ analysis build with switchable arithmetic that produced that table -- the float64 pin of
+// tests/test_gpu_blend_pairs.py does its job now -- and the variant of this body with `power` on three v_pk_*_f32, 30 instructions,
+// bit-identical and 5 % slower: profiles/r06_fwd_pk_ab.txt.)
+#define SGR_FWD_BODY_X(X, Y, A, B, CZ, OP, R, G, BL, POS)                                           \
     "v_sub_f32 v60, " X ", %[px]\n"                                                                 \
     "v_sub_f32 v61, " Y ", %[py]\n"                                                                 \
     "v_mul_f32 v62, " A ", v60\n"                                                                   \
@@ -171,51 +174,8 @@ __device__ __forceinline__ bool block_hit(float gxc, float gyc, float cx, float 
     "v_mov_b32 %[last], " POS "\n"                                                                  \
     "s_mov_b64 exec, %[live]\n"
 
-// A/B build option -DSGR_FWD_PK (round-5 verdict item 5, "build one instruction-diet variant"): the exact body with `power` on
-// packed arithmetic -- (dx, dy), (cx' dx, cz' dy) and their squares as three v_pk_*_f32 instead of six scalar operations; the entry
-// then carries (-0.5 cx, -0.5 cz) as a register pair and cy behind them.  Same operations on the same values: bit-identical.
-// 30 instead of 33 vector instructions per entry; profiles/r06_fwd_pk_ab.txt has what that bought.
-#define SGR_FWD_BODY_XPK(X, Y, A, B, CZ, OP, R, G, BL, POS, XY, AB)                                  \
-    "v_pk_add_f32 v[60:61], " XY ", %[pxy] neg_lo:[0,1] neg_hi:[0,1]\n"                              \
-    "v_pk_mul_f32 v[62:63], " AB ", v[60:61]\n"                                                      \
-    "v_pk_mul_f32 v[62:63], v[62:63], v[60:61]\n"                                                    \
-    "v_mul_f32 v60, " CZ ", v60\n"      /* cy dx  (CZ holds cy in this layout) */                   \
-    "v_add_f32 v62, v62, v63\n"                                                                     \
-    "v_mul_f32 v60, v60, v61\n"                                                                     \
-    "v_sub_f32 v63, v62, v60\n"         /* power */                                                 \
-    "v_mul_f32 v60, 0x3fb8aa3b, v63\n"                                                              \
-    "v_rndne_f32 v61, v60\n"                                                                        \
-    "v_fma_f32 v62, v63, %[chi], -v60\n"                                                            \
-    "v_fmac_f32 v62, 0x32a5705f, v63\n"                                                             \
-    "v_sub_f32 v60, v60, v61\n"                                                                     \
-    "v_add_f32 v60, v60, v62\n"                                                                     \
-    "v_exp_f32 v60, v60\n"                                                                          \
-    "v_cvt_i32_f32 v61, v61\n"                                                                      \
-    "s_mov_b64 %[live], exec\n"                                                                     \
-    "v_cmp_nlt_f32 vcc, 0, v63\n"                                                                   \
-    "v_ldexp_f32 v62, v60, v61\n"                                                                   \
-    "v_mul_f32 v62, " OP ", v62\n"                                                                  \
-    "v_min_f32 v62, 0x3f7d70a4, v62\n"                                                              \
-    "s_and_b64 exec, exec, vcc\n"                                                                   \
-    "v_cmp_ngt_f32 vcc, 0x3b808081, v62\n"                                                          \
-    "v_sub_f32 v60, 1.0, v62\n"                                                                     \
-    "v_mul_f32 v61, v62, %[T]\n"                                                                    \
-    "v_mul_f32 v60, %[T], v60\n"                                                                    \
-    "s_and_b64 exec, exec, vcc\n"                                                                   \
-    "v_cmp_gt_f32 vcc, 0x38d1b717, v60\n"                                                           \
-    "s_andn2_b64 %[live], %[live], vcc\n"                                                           \
-    "s_andn2_b64 exec, exec, vcc\n"                                                                 \
-    "v_mov_b32 %[T], v60\n"                                                                         \
-    "v_fmac_f32 %[C0], " R ", v61\n"                                                                \
-    "v_fmac_f32 %[C1], " G ", v61\n"                                                                \
-    "v_fmac_f32 %[C2], " BL ", v61\n"                                                               \
-    "v_mov_b32 %[last], " POS "\n"                                                                  \
-    "s_mov_b64 exec, %[live]\n"
-
 #define SGR_FWD_ENTRY_BYTES 48
 
-
-#ifndef SGR_BLEND_CXX
 #define SGR_FWD_WALK_ASM(BODY)                                                                                                 \
         "s_mov_b64 %[full], exec\n"                                                                                            \
         "s_and_b64 exec, exec, %[live]\n"                                                                                      \
@@ -228,7 +188,7 @@ __device__ __forceinline__ bool block_hit(float gxc, float gyc, float cx, float 
         "ds_read_b128 v[54:57], %[addr] offset:64\n"                                                                           \
         "ds_read_b64 v[58:59], %[addr] offset:80\n"                                                                            \
         "s_waitcnt lgkmcnt(3)\n"                                                                                               \
-        BODY("v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v[40:41]", "v[42:43]")                      \
+        BODY("v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49")                                              \
         "s_cbranch_execz 3f\n"                                                                                                 \
         "s_add_i32 %[n], %[n], -1\n"                                                                                           \
         "s_cmp_eq_u32 %[n], 0\n"                                                                                               \
@@ -238,7 +198,7 @@ __device__ __forceinline__ bool block_hit(float gxc, float gyc, float cx, float 
         "ds_read_b64 v[48:49], %[addr] offset:128\n"                                                                           \
         "v_add_u32 %[addr], 96, %[addr]\n"                                                                                     \
         "s_waitcnt lgkmcnt(3)\n"                                                                                               \
-        BODY("v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v[50:51]", "v[52:53]")                      \
+        BODY("v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59")                                              \
         "s_cbranch_execz 3f\n"                                                                                                 \
         "s_add_i32 %[n], %[n], -1\n"                                                                                           \
         "s_cmp_eq_u32 %[n], 0\n"                                                                                               \
@@ -257,90 +217,11 @@ __device__ __forceinline__ void fwd_walk(uint32_t addr, int& n, unsigned long lo
                                          float& C0, float& C1, float& C2, uint32_t& last)
 {
     unsigned long long full;
-    const unsigned long long pixxy = ((unsigned long long)__float_as_uint(pixfy) << 32) | (unsigned long long)__float_as_uint(pixfx);  // (px, py) as a register pair
-#ifdef SGR_FWD_PK
-    if constexpr (EXACT) asm volatile(SGR_FWD_WALK_ASM(SGR_FWD_BODY_XPK) SGR_FWD_WALK_OPERANDS);
-#else
+    // (pixxy / [pxy]: dead, but dropping it changes the register allocation of all four one-wave forward kernels: measure before removing)
+    const unsigned long long pixxy = ((unsigned long long)__float_as_uint(pixfy) << 32) | (unsigned long long)__float_as_uint(pixfx);
     if constexpr (EXACT) asm volatile(SGR_FWD_WALK_ASM(SGR_FWD_BODY_X) SGR_FWD_WALK_OPERANDS);
-#endif
     else asm volatile(SGR_FWD_WALK_ASM(SGR_FWD_BODY) SGR_FWD_WALK_OPERANDS);
 }
-#endif
-
-#ifdef SGR_BLEND_CXX
-// ---- ANALYSIS BUILD (SGR_BLEND_DEFS="-DSGR_BLEND_CXX=<mask>", scripts/r06_grad_switches.sh): the two hand-scheduled walks as plain
-// C++, with the places where their arithmetic departs from the reference's (forward.cu:330-366, backward.cu:486-554, compiled without
-// contraction) switchable one by one, to find which departure carries the gradient error of tests/test_gpu_fullsize.py.  Mask 0
-// reproduces the assembly bit for bit.  Not a product path: slower, and never built by default.
-//   1  power from the raw conic in the reference's operation order (ours: conic pre-scaled by log2 e, two FMAs)
-//   2  G = expf(power) (needs 1; ours: v_exp_f32 of the pre-scaled power)
-//   4  test_T = T * (1 - alpha)  (ours: T - alpha * T)
-//   8  C += (c * alpha) * T, unfused  (ours: fma(c, alpha * T, C))
-//  16  T = T / (1 - alpha)  (ours: T * v_rcp_f32(1 - alpha))
-//  32  accum_rec per channel and the background term as in backward.cu:514-534 (ours: the scalar recurrence on colour . g)
-//  64  phase B's moment sums in double
-#define SGR_X(bit) ((SGR_BLEND_CXX) & (bit))
-#pragma clang fp contract(off)
-__device__ __forceinline__ float x_power_G(const float* e, float dx, float dy, float& power_sign)
-{
-#if SGR_X(1)
-    const float power = -0.5f * (e[2] * dx * dx + e[4] * dy * dy) - e[3] * dx * dy;
-    power_sign = power;
-#if SGR_X(2)
-    return expf(power);
-#else
-    return __builtin_amdgcn_exp2f(power * LOG2E);
-#endif
-#else
-    const float t = __builtin_fmaf(e[2], dx, e[3] * dy);
-    const float p2 = __builtin_fmaf(dx, t, (e[4] * dy) * dy);
-    power_sign = p2;
-    return __builtin_amdgcn_exp2f(p2);
-#endif
-}
-__device__ __forceinline__ void fwd_walk_cxx(const float* s_e, int& n, unsigned long long& live, float pixfx, float pixfy, float& T,
-                                             float& C0, float& C1, float& C2, uint32_t& last)
-{
-    const int lane = threadIdx.x;
-    const int n0 = n;
-    for (int k = 0; k < n0; k++) {
-        const float* e = s_e + k * (SGR_FWD_ENTRY_BYTES / 4);
-        const bool act = (live >> lane) & 1ull;
-        bool fin = false;
-        if (act) {
-            const float dx = e[0] - pixfx, dy = e[1] - pixfy;
-            float ps;
-            const float G = x_power_G(e, dx, dy, ps);
-            if (!(ps > 0.f)) {
-                const float alpha = fminf(0.99f, e[5] * G);
-                if (!(alpha < 1.0f / 255.0f)) {
-#if SGR_X(4)
-                    const float test_T = T * (1.f - alpha);
-                    const float aT = alpha * T;
-#else
-                    const float aT = alpha * T;
-                    const float test_T = T - aT;
-#endif
-                    if (test_T < 0.0001f) fin = true;
-                    else {
-#if SGR_X(8)
-                        C0 += e[6] * alpha * T; C1 += e[7] * alpha * T; C2 += e[8] * alpha * T;
-#else
-                        C0 = __builtin_fmaf(e[6], aT, C0); C1 = __builtin_fmaf(e[7], aT, C1); C2 = __builtin_fmaf(e[8], aT, C2);
-#endif
-                        T = test_T;
-                        last = __float_as_uint(e[9]);
-                    }
-                }
-            }
-        }
-        live &= ~__ballot(fin);
-        if (live == 0ull) { n = n0 - k; return; }
-    }
-    n = 0;
-}
-#pragma clang fp contract(fast)
-#endif  // SGR_BLEND_CXX
 
 template <bool REPAIR, bool EXACT>
 __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ tile_start,
@@ -404,7 +285,9 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
     // (round 5: the ids run TWO batches ahead.  With one batch of lead the id load of batch b + 1, issued at the top of iteration b,
     // had only that iteration's cull and walk to come back in -- a fraction of a microsecond when few entries survive the cull --
     // so every batch paid two dependent memory round trips, ids then records: a tile that walks thousands of entries, a silhouette
-    // tile of BASELINE config 4's flat splats walks 4 700, is a chain of ~3 us links and the whole launch waits for it.)
+    // tile of BASELINE config 4's flat splats walks 4 700, is a chain of ~3 us links and the whole launch waits for it.
+    // The RECORDS one batch ahead as well bought config 4 5 % of the forward and cost the metric workload 6 %
+    // (profiles/r05_blend_pipelining_ab.txt): that variant was removed, it last existed in c4def3b.)
     uint32_t id_next = 0u, id_next2 = 0u;
     if (total > 0) {  // (uniform branch)
         id_next = point_list[r0 + (uint32_t)min(lane, total - 1)];
@@ -415,60 +298,25 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
     // batch b of the tile sits in slot (r0 >> 6) + tile + b: slots of different tiles never overlap)
     unsigned long long* my_mask = blk_mask + 4 * ((size_t)(r0 >> 6) + (size_t)tile) + sub;
     int n_batches = 0;
-#ifdef SGR_FWD_PREFETCH_RECORDS
-    // (A/B build option, round 5: the RECORDS of batch b + 1 are requested before batch b is culled and walked -- twelve more live
-    // registers across the walk.  For the one wave of a tile that walks thousands of entries the gather's round trip is then off
-    // the chain; see DESIGN.md for what it did to the metric workload and to config 4)
-    float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0;
-    uint32_t id_pref = id_next;  // whose records p0 .. p2 hold
-    if (total > 0) {
-        const float4* rp0 = reinterpret_cast<const float4*>(rec + id_next);
-        p0 = rp0[0]; p1 = rp0[1]; p2 = rp0[2];
-        id_next = id_next2;
-        id_next2 = point_list[r0 + (uint32_t)min(128 + lane, total - 1)];
-    }
-#endif
     for (int base = 0; base < total && live != 0ull; base += 64) {
-#ifdef SGR_FWD_PREFETCH_RECORDS
-        const float4 v0 = p0, v1 = p1, v2 = p2;
-        const uint32_t id_cur = id_pref;
-        id_pref = id_next;
-        {
-            const float4* rp = reinterpret_cast<const float4*>(rec + id_next);   // batch b + 1 (clamped ids past the end: a cached line)
-            p0 = rp[0]; p1 = rp[1]; p2 = rp[2];
-        }
-        id_next = id_next2;
-        id_next2 = point_list[r0 + (uint32_t)min(base + 192 + lane, total - 1)];
-#else
         const uint32_t id_cur = id_next;  // (kept for the reach flag below: id_next moves on)
         const float4* rp = reinterpret_cast<const float4*>(rec + id_cur);
         const float4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
         id_next = id_next2;
         id_next2 = point_list[r0 + (uint32_t)min(base + 128 + lane, total - 1)];
-#endif
         const bool hit = (base + lane < total) && block_hit(v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, (float)bx0, (float)by0);
         const unsigned long long m = __ballot(hit);
         int n = __popcll(m);
         if (hit) {
             const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             float4* e = reinterpret_cast<float4*>(s_e + pos * (SGR_FWD_ENTRY_BYTES / 4));
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 1)
-            e[0] = make_float4(v0.x, v0.y, v0.z, v0.w);   // (analysis build: the raw conic)
-            e[1] = make_float4(v1.x, v1.y, v2.x, v2.y);
-#else
             if (EXACT) {  // the raw conic, the two halvings applied (exact): SGR_FWD_BODY_X
-#ifdef SGR_FWD_PK
-                e[0] = make_float4(v0.x, v0.y, -0.5f * v0.z, -0.5f * v1.x);   // (-0.5 cx, -0.5 cz) as a pair, cy behind them
-                e[1] = make_float4(v0.w, v1.y, v2.x, v2.y);
-#else
                 e[0] = make_float4(v0.x, v0.y, -0.5f * v0.z, v0.w);
                 e[1] = make_float4(-0.5f * v1.x, v1.y, v2.x, v2.y);
-#endif
             } else {
                 e[0] = make_float4(v0.x, v0.y, -0.5f * LOG2E * v0.z, -LOG2E * v0.w);
                 e[1] = make_float4(-0.5f * LOG2E * v1.x, v1.y, v2.x, v2.y);
             }
-#endif
             *reinterpret_cast<float2*>(e + 2) = make_float2(v2.z, __uint_as_float((uint32_t)(base + lane + 1)));
             // reach flag (sh_adam_update.h): this Gaussian has a survivor bit in the mask written below, so the blend backward may reach
             // it.  The same value from many waves: a plain byte store.
@@ -480,11 +328,7 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
         __builtin_amdgcn_wave_barrier();
         if (n > 0) {
             const int n0 = n;
-#ifdef SGR_BLEND_CXX
-            fwd_walk_cxx(s_e, n, live, pixfx, pixfy, T, C0, C1, C2, last_contributor);
-#else
             fwd_walk<EXACT>(lds0, n, live, pixfx, pixfy, T, C0, C1, C2, last_contributor);
-#endif
             if (live == 0ull) {  // every pixel finished at compacted entry n0 - n: its list position is the furthest examined
                 walked = __float_as_uint(s_e[(n0 - n) * (SGR_FWD_ENTRY_BYTES / 4) + 9]);
                 break;
@@ -508,15 +352,9 @@ __device__ __forceinline__ void blend_fwd_body(int W, int H, int gx, int T_tiles
         const size_t HW = (size_t)H * W;
         final_T[pix_id] = T;
         n_contrib[pix_id] = last_contributor;
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 8)
-        out_color[pix_id] = __fadd_rn(C0, __fmul_rn(T, bg[0]));
-        out_color[HW + pix_id] = __fadd_rn(C1, __fmul_rn(T, bg[1]));
-        out_color[2 * HW + pix_id] = __fadd_rn(C2, __fmul_rn(T, bg[2]));
-#else
         out_color[pix_id] = C0 + T * bg[0];
         out_color[HW + pix_id] = C1 + T * bg[1];
         out_color[2 * HW + pix_id] = C2 + T * bg[2];
-#endif
     }
     // deepest contributor / furthest examined position of the TILE (zeroed by the launcher): maximum over its four blocks
     uint32_t mc = inside ? last_contributor : 0u;
@@ -871,7 +709,6 @@ k_blend_fwd_deep(SGR_FWD_PARAMS, const uint32_t* __restrict__ tile_need, const u
     "ds_write_b64 %[waddr], " XY OFF "\n"
 
 // rows (1..BW_SUB) queue entries starting at LDS address e_addr -> panel rows 0..rows-1 at w_addr (+ 8 * lane already added)
-#ifndef SGR_BLEND_CXX
 #define SGR_BWD_WALK_ASM(HEAD)                                                                                                  \
         "s_mov_b64 %[full], exec\n"                                                                                             \
         "s_waitcnt lgkmcnt(0)\n"                                                                                                \
@@ -915,62 +752,6 @@ __device__ __forceinline__ void bwd_phase_a(uint32_t e_addr, uint32_t w_addr, in
     if constexpr (EXACT) asm volatile(SGR_BWD_WALK_ASM(SGR_BWD_HEAD_X) SGR_BWD_WALK_OPERANDS);
     else asm volatile(SGR_BWD_WALK_ASM(SGR_BWD_HEAD) SGR_BWD_WALK_OPERANDS);
 }
-#endif
-
-#ifdef SGR_BLEND_CXX
-struct XBwd { float accum_rec[3] = {0.f, 0.f, 0.f}, last_alpha = 0.f, last_color[3] = {0.f, 0.f, 0.f}; };
-#pragma clang fp contract(off)
-__device__ __forceinline__ void bwd_phase_a_cxx(const float* q, float2* zw, int rows, unsigned long long inside_mask, float pixfx, float pixfy,
-                                                float g0, float g1, float g2, float ntb, uint32_t lastc, float& T, float& acc_g, XBwd& st,
-                                                const float* bg, float T_final)
-{
-    const int lane = threadIdx.x;
-    const bool inside = (inside_mask >> lane) & 1ull;
-    for (int r = 0; r < rows; r++) {
-        const float* e = q + r * BW_ENTRY_DW;
-        const float dx = e[0] - pixfx, dy = e[1] - pixfy;
-        float ps;
-        const float G = x_power_G(e, dx, dy, ps);
-        const float alpha = fminf(0.99f, e[5] * G);
-        float Z = 0.f, Wt = 0.f;
-        if (!(ps > 0.f) && __float_as_uint(e[9]) <= lastc && inside && !(alpha < 1.0f / 255.0f)) {
-#if SGR_X(16)
-            T = T / (1.f - alpha);
-            const float B = 1.f / (1.f - alpha);
-#else
-            const float B = __builtin_amdgcn_rcpf(1.f - alpha);
-            T = T * B;
-#endif
-            Wt = alpha * T;
-            float dLda;
-#if SGR_X(32)
-            const float c[3] = {e[6], e[7], e[8]}, g[3] = {g0, g1, g2};
-            dLda = 0.f;
-            for (int ch = 0; ch < 3; ch++) {
-                st.accum_rec[ch] = st.last_alpha * st.last_color[ch] + (1.f - st.last_alpha) * st.accum_rec[ch];
-                st.last_color[ch] = c[ch];
-                dLda += (c[ch] - st.accum_rec[ch]) * g[ch];
-            }
-            dLda *= T;
-            st.last_alpha = alpha;
-            float bg_dot = 0.f;
-            for (int i = 0; i < 3; i++) bg_dot += bg[i] * g[i];
-            dLda += (-T_final / (1.f - alpha)) * bg_dot;
-            (void)B; (void)ntb;
-#else
-            const float cg = __builtin_fmaf(e[8], g2, __builtin_fmaf(e[7], g1, e[6] * g0));
-            float d = cg - acc_g;
-            acc_g = __builtin_fmaf(alpha, d, acc_g);
-            d = d * T;
-            dLda = __builtin_fmaf(ntb, B, d);
-#endif
-            Z = G * dLda;
-        }
-        zw[r * BW_ZW_STRIDE] = make_float2(Z, Wt);
-    }
-}
-#pragma clang fp contract(fast)
-#endif
 
 template <bool EXACT>
 __device__ __forceinline__ void
@@ -1050,24 +831,14 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
     const uint32_t q_lds = (uint32_t)(uintptr_t)s_q;
     const uint32_t zw_lds = (uint32_t)(uintptr_t)s_zw + 8u * (uint32_t)lane;
 
-#ifdef SGR_BLEND_CXX
-    XBwd xst;
-#endif
     int qn = 0;  // entries waiting in the queue (they sit at its front)
     // the queued entries in groups of BW_SUB (all of them at the end, full groups only before), the rest moves to the front
     auto drain = [&](const bool last_batch) {
         int qs = 0;
         while (qn - qs >= BW_SUB || (last_batch && qn > qs)) {
             const int rows = min(BW_SUB, qn - qs);
-#ifdef SGR_BLEND_CXX
-            bwd_phase_a_cxx(s_q + qs * BW_ENTRY_DW, s_zw + lane, rows, inside_mask, pixfx, pixfy, g0, g1, g2, ntb, last_contributor, T, acc_g,
-                            xst, bg, T_final);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#else
             bwd_phase_a<EXACT>(q_lds + (uint32_t)qs * (BW_ENTRY_DW * 4), zw_lds, rows, inside_mask, pixfx, pixfy, g0, g1, g2, ntb,
                                last_contributor, T, acc_g);
-#endif
             // ---------------- phase B: lane = (panel row bg_, pixel rows 2 bq and 2 bq + 1)
             if (bg_ < rows) {
                 const float* e = s_q + (qs + bg_) * BW_ENTRY_DW;
@@ -1079,31 +850,19 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
                 // 5e-8).  xb - xc is exact, and every product below is of the size of the moment it contributes to.
                 const float xb = e[0] - (float)bx0, yb = e[1] - (float)by0;
                 const float xc = rintf(xb), yc = rintf(yb);
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 64)
-                double s0 = 0., sx = 0., sxx = 0., k0 = 0., k1 = 0., k2 = 0.;   // (analysis build)
-#else
                 float s0 = 0.f, sx = 0.f, sxx = 0.f, k0 = 0.f, k1 = 0.f, k2 = 0.f;
-#endif
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
                     const float2 v = row[i];
                     const float t = (float)i - xc;
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 64)
-                    const double u = (double)v.x * t;
-#else
                     const float u = v.x * t;
-#endif
                     s0 += v.x; sx += u; sxx += u * t;
                     k0 += v.y * rg0[i]; k1 += v.y * rg1[i]; k2 += v.y * rg2[i];
                 }
                 // this lane's share of the moments (its pixels all have y = bq), shifted from (xc, yc) to the Gaussian's centre,
                 // d = centre - pixel = (xb - x, yb - y) -- the shift is linear in the moments, so it is applied to the shares and the
                 // shifted shares are summed over the eight lanes of the Gaussian
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 64)
-                typedef double mom_t;
-#else
                 typedef float mom_t;
-#endif
                 const mom_t y0 = (float)bq - yc;
                 const mom_t sy = y0 * s0, sxy = y0 * sx, syy = y0 * sy;
                 const mom_t xr = xb - xc, yr = yb - yc;
@@ -1194,10 +953,6 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
             // back to front: rank = taken lanes ABOVE this one
             const uint32_t slot = (uint32_t)qn + (uint32_t)__popcll(lane == 63 ? 0ull : (m >> (lane + 1)));
             float4* e = reinterpret_cast<float4*>(s_q + slot * BW_ENTRY_DW);
-#if defined(SGR_BLEND_CXX) && ((SGR_BLEND_CXX) & 1)
-            e[0] = make_float4(v0.x, v0.y, v0.z, v0.w);
-            e[1] = make_float4(v1.x, v1.y, v2.x, v2.y);
-#else
             if (EXACT) {
                 e[0] = make_float4(v0.x, v0.y, -0.5f * v0.z, v0.w);
                 e[1] = make_float4(-0.5f * v1.x, v1.y, v2.x, v2.y);
@@ -1205,7 +960,6 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
                 e[0] = make_float4(v0.x, v0.y, -0.5f * LOG2E * v0.z, -LOG2E * v0.w);
                 e[1] = make_float4(-0.5f * LOG2E * v1.x, v1.y, v2.x, v2.y);
             }
-#endif
             e[2] = make_float4(v2.z, __uint_as_float(pos), __uint_as_float(id_cur), 0.f);
         }
         qn += __popcll(m);
@@ -1221,13 +975,10 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
         const float *__restrict__ final_Ts, const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix,                      \
         float *__restrict__ acc, const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ header, uint32_t list_cap
 #define SGR_BWD_ARGS W, H, gx, T_tiles, tile_start, point_list, binning, blk_nb, rec, bg, final_Ts, n_contrib, dL_dpix, acc, tile_order, header, list_cap
-#ifdef SGR_BWD_WAVES   // (A/B build option: force the waves per SIMD the register allocation aims at)
-#define SGR_BWD_OCC __attribute__((amdgpu_waves_per_eu(SGR_BWD_WAVES, SGR_BWD_WAVES)))
-#else
-#define SGR_BWD_OCC
-#endif
-__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_w(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<false>(SGR_BWD_ARGS, job); }
-__global__ void __launch_bounds__(64) SGR_BWD_OCC k_blend_bwd_wx(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<true>(SGR_BWD_ARGS, job); }  // exact alpha (SGR_BWD_HEAD_X)
+// (Forcing the waves per SIMD the register allocation aims at: one fewer costs 4.6 %, one more spills --
+// profiles/r06_blend_bwd_occupancy_ab.txt; the build option for it was removed, it last existed in c4def3b.)
+__global__ void __launch_bounds__(64) k_blend_bwd_w(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<false>(SGR_BWD_ARGS, job); }
+__global__ void __launch_bounds__(64) k_blend_bwd_wx(SGR_BWD_PARAMS, SgrShAdamJob job) { blend_bwd_body<true>(SGR_BWD_ARGS, job); }  // exact alpha (SGR_BWD_HEAD_X)
 
 // Launch order of the backward: tiles by how deep the forward walked them (tile_maxc), deepest first, so that the waves still
 // running when the grid drains are the short ones.  (Workgroups start in index order; with ~2.5 dispatch rounds of waves whose
@@ -1318,7 +1069,7 @@ void sgr_launch_blend_fwd_post(int gx, int gy, const uint32_t* tile_maxc, const 
     const int T = gx * gy;
     if (order_out) {
         SgrTileOrderJob job = {T, list_cap, tile_maxc, tile_need_out ? tile_walked : nullptr, header, order_scratch, order_out, tile_need_out,
-                               header_host_dev, hint_margin > 0.f ? hint_margin : 0.25f, gx, gy};
+                               header_host_dev, hint_margin > 0.f ? hint_margin : 0.25f};
         hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, job);
         return;
     }
@@ -1336,7 +1087,6 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
     const int T = gx * gy;
     SgrShAdamJob job = {};
     unsigned grid = sgr_blend_grid(T);
-#ifndef SGR_SLOT_RUNS
     if (job_in && job_in->P > 0 && job_in->k >= 8 && (job_in->k & 7) == 0) {
         job = *job_in;
         const int n_adam = (job.P + 63) / 64;
@@ -1344,15 +1094,14 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
         job.n_with = n_adam / job.k < job.n_groups ? n_adam / job.k : job.n_groups;
         grid += (unsigned)n_adam;
     }
-#endif
     if (order_ready) {}                           // (the forward sorted: sgr_forward_opts.tile_order_out)
     else if (4 * T < 8192) tile_order = nullptr;  // (fewer waves than the chip holds at once: nothing to order)
     else {
-        SgrTileOrderJob order_job = {T, list_cap, tile_maxc, nullptr, header, tile_order, nullptr, nullptr, nullptr, 0.f, gx, gy};
+        SgrTileOrderJob order_job = {T, list_cap, tile_maxc, nullptr, header, tile_order, nullptr, nullptr, nullptr, 0.f};
         hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, order_job);
     }
     hipLaunchKernelGGL(exact ? k_blend_bwd_wx : k_blend_bwd_w, dim3(grid), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, binning, blk_nb, rec,
                        bg, final_T, n_contrib, dL_dpix, acc, tile_order, header, list_cap, job);
-    // (a job this launch could not carry -- k no multiple of 8, a build with other slot runs -- is still done: a launch of its own)
+    // (a job this launch could not carry -- k no multiple of 8 -- is still done: a launch of its own)
     if (job_in && job_in->P > 0 && job.P == 0) sgr_launch_sh_adam_zero(*job_in, s);
 }

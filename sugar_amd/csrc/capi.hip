@@ -283,8 +283,6 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
     }
     if ((flags & SGR_FLAG_DEFER_POST) && opts->header_host && !hh_dev)  // (checked before anything is enqueued)
         return fail(SGR_E_INVALID, "SGR_FLAG_DEFER_POST needs a device-mapped header_host");
-    // (SGR_NO_HINT_REPAIR=1: a tile that outruns its walk hint invalidates the forward, as until round 4 -- an A/B switch)
-    static const bool hint_repair = getenv("SGR_NO_HINT_REPAIR") == nullptr;
     PreprocessArgs pa;
     pa.P = P; pa.D = D; pa.M = shs ? M : 0;
     pa.means3D = means3D; pa.scales = scales; pa.scale_modifier = scale_modifier; pa.rotations = rotations;
@@ -299,7 +297,7 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
     pa.rect_by_id = reinterpret_cast<uint2*>(sort_scratch + sgr_sort_rect_by_id_offset(P));
     pa.key_minmax = reinterpret_cast<uint2*>(sort_scratch + sgr_sort_minmax_offset(P));
     pa.sort_counters = reinterpret_cast<uint32_t*>(sort_scratch + sgr_sort_counters_offset(P)); pa.n_sort_counters = sgr_sort_counter_words();
-    if (opts->tile_need && hint_repair) { pa.zero_words = repair_flag; pa.n_zero_words = IL.T; }  // (the walk hint's repair flags start from zero)
+    if (opts->tile_need) { pa.zero_words = repair_flag; pa.n_zero_words = IL.T; }  // (the walk hint's repair flags start from zero)
     // Sort beside preprocess (round 6): the depth keys come from a 12-byte-per-Gaussian kernel of their own on a side stream, which
     // also runs the sort's histogram kernel and its first two passes while the HBM-bound preprocess kernel streams on the caller's;
     // the caller's stream joins before the sort's last pass (it carries the rectangles the preprocess kernel writes).
@@ -400,17 +398,17 @@ int64_t sgr_forward_ex(sgr_alloc_fn geom_alloc, void* geom_user, sgr_alloc_fn bi
                 sgr_launch_blend_fwd_deep(width, height, IL.gx, IL.gy, tile_start, point_list, rec, background, final_T, n_contrib, tile_maxc,
                                           tile_walked, out_color, blk_mask, blk_nb, header, (uint32_t)R_, opts->tile_need,
                                           reinterpret_cast<uint32_t*>(img + IL.deep_list), deep_min, dside->st,
-                                          hint_repair ? repair_flag : nullptr, repair_list, exact);
+                                          repair_flag, repair_list, exact);
                 HIP_TRY(hipEventRecord(dside->join, dside->st));
             }
             sgr_launch_blend_fwd(width, height, IL.gx, IL.gy, tile_start, point_list, rec, background, final_T, n_contrib,
                                  tile_maxc, tile_walked, out_color, blk_mask, blk_nb, header, (uint32_t)R_, opts->tile_need,
-                                 opts->tile_order, s, hint_repair ? repair_flag : nullptr, repair_list, exact, deep_min, reach);
+                                 opts->tile_order, s, repair_flag, repair_list, exact, deep_min, reach);
             if (dside) HIP_TRY(hipStreamWaitEvent(s, dside->join, 0));
         }   // (that stage timer -- bench.py's roofline.launch_ms -- brackets k_blend_fwd_w alone; the two gated launches are a stage of their own)
         {
             SgrStageTimer t(s, SGR_STAGE_HINT_REPAIR);
-            if (opts->tile_need && two_level && R_ > 0 && hint_repair) {
+            if (opts->tile_need && two_level && R_ > 0) {
                 // Walk-hint repair: tiles that outran their hint are on the device's repair list now.  The list-write pass once more
                 // with the repair flags as ITS hint (0: nothing needed; 0xFFFFFFFF: the whole list) and the blend once more over the
                 // listed tiles' full lists -- both gated on the list's count, i.e. two empty launches when every hint held.  A hint
@@ -530,8 +528,6 @@ int sgr_forward_post_job(int width, int height, char* img_buffer, int64_t R, con
     job->need_out = opts->tile_need_out;
     job->header_host = hh_dev;
     job->margin = opts->hint_margin > 0.f ? opts->hint_margin : 0.25f;
-    job->gx = IL.gx;
-    job->gy = IL.gy;
     return 0;
 }
 

@@ -1,6 +1,5 @@
 // tile_order.h -- behind a blend forward, by ONE workgroup of NT threads: this view's launch order (tiles by the depth of their
-// deepest contributor, deepest first: a counting sort over 1024 depth classes, ties in arbitrary order; a build with
-// -DSGR_ORDER_SUPER_TILE orders whole 8x8-tile super-tiles instead, see below), the walk hint for the
+// deepest contributor, deepest first: a counting sort over 1024 depth classes, ties in arbitrary order), the walk hint for the
 // camera's next visit and the second header copy for the host (include/sugar_raster.h: sgr_forward_opts.tile_order_out,
 // tile_need_out, header_host).  Device code shared by blend.hip (a kernel of its own: k_tile_order) and loss.hip (a spare
 // workgroup of the loss forward kernel, which is what follows the blend in the train step: the 12 us of this serial,
@@ -19,41 +18,22 @@ struct SgrTileOrderJob {
     uint32_t* need_out;          // walk hint out, or NULL
     uint32_t* header_host;       // device address of the pinned header copy, or NULL
     float margin;
-    int gx, gy;                  // tile grid (0: order tile by tile)
 };
 
 // Workgroup b of a blend kernel runs on XCD b % 8.  Slot -> workgroup mapping shared by both blend kernels: the four 8x8 blocks of a
 // tile on one XCD, consecutive slots on consecutive XCDs.
-// Round 4 measured the alternative the round-3 verdict asked for -- launch order at SUPER-TILE granularity (-DSGR_ORDER_SUPER_TILE:
-// 8x8-tile super-tiles deepest first, raster order inside) with runs of 8 / 16 / 32 / 64 consecutive slots per XCD (-DSGR_SLOT_RUNS
-// -DSGR_SLOT_RUN=n), so that the tiles that share Gaussian records run at the same time on the same L2.  Same box, alternating
-// runs (profiles/r04_launch_order_ab.txt): FETCH_SIZE of the forward blend 112 -> 55 / 37 / 30 / 30 MiB as counted (HBM traffic
-// 283 -> 114 MB, 0.85x the algorithmic bytes), of the backward 94 -> 53 / 44 / 39 / 38 -- and the kernels SLOWER: forward 110.0 ->
-// 113.1 / 112.7 / 113.8 / 116.4 us, backward 198.7 -> 210.7 / 209.0 / 211.8 / 213.2, step 1.005 -> 1.02 ms.  (Per-tile depth order
-// with runs of 64: 114.6 / 204.8 us.)  The kernels are bound by their vector work and its tail, not by memory: the per-tile
-// order stays the default, the alternative stays buildable.
-#ifndef SGR_SLOT_RUN
-#define SGR_SLOT_RUN 64  // consecutive slots per XCD (a power of two up to 64)
-#endif
+// Round 4 measured the alternative -- whole 8x8-tile super-tiles deepest first, runs of 8 .. 64 consecutive slots per XCD, so that
+// tiles that share Gaussian records share an L2: the blends' fetched bytes fell by half and more and both kernels got SLOWER on every
+// setting (profiles/r04_launch_order_ab.txt).  They are bound by their vector work and its tail, not by memory; that variant was
+// removed (it last existed in c4def3b).
 __device__ __forceinline__ void sgr_slot_of_workgroup(int wg, int& slot, int& sub)
 {
-#ifndef SGR_SLOT_RUNS  // (default: consecutive slots on consecutive XCDs; -DSGR_SLOT_RUNS: runs of SGR_SLOT_RUN slots per XCD)
     sub = (wg >> 3) & 3;
     slot = ((wg >> 5) << 3) + (wg & 7);
-#else
-    const int x = wg & 7, i = wg >> 3;
-    sub = i & 3;
-    const int q = i >> 2;
-    slot = (q / SGR_SLOT_RUN) * (8 * SGR_SLOT_RUN) + x * SGR_SLOT_RUN + (q % SGR_SLOT_RUN);
-#endif
 }
 static inline unsigned sgr_blend_grid(int T)
 {
-#ifndef SGR_SLOT_RUNS
     return 32u * (unsigned)((T + 7) / 8);
-#else
-    return 2048u * (unsigned)((T + 511) / 512);
-#endif
 }
 
 template <int NT>
@@ -86,45 +66,6 @@ __device__ __forceinline__ void sgr_tile_order_block(const SgrTileOrderJob& j)
             __syncthreads();
         }
     }
-#ifdef SGR_ORDER_SUPER_TILE
-    // ---- order at SUPER-TILE granularity: the 8x8-tile super-tiles by the depth of their deepest tile, deepest first, the tiles
-    // of a super-tile in raster order behind one another (consecutive slots: one XCD, see sgr_slot_of_workgroup).  Depth is
-    // spatially coherent, so starting the deep REGIONS first keeps what the per-tile order bought (the tail of long-lived
-    // waves) while neighbouring tiles run at the same time on the same L2 again.  Up to 512 super-tiles (4K): two tables in s_cls.
-    const int sgx = (j.gx + SGR_SUP - 1) / SGR_SUP, sgy = (j.gy + SGR_SUP - 1) / SGR_SUP, S = sgx * sgy;
-    if (j.gx > 0 && S <= 512) {
-        uint32_t* s_depth = s_cls;        // deepest contributor over the super-tile's tiles
-        uint32_t* s_start = s_cls + 512;  // first slot of the super-tile
-        for (int c = tid; c < S; c += NT) s_depth[c] = 0u;
-        __syncthreads();
-        for (int i = tid; i < T; i += NT) {
-            const int tx = i % j.gx, ty = i / j.gx;
-            atomicMax(&s_depth[(ty >> SGR_SUP_SHIFT) * sgx + (tx >> SGR_SUP_SHIFT)], j.tile_maxc[i]);
-        }
-        __syncthreads();
-        for (int c = tid; c < S; c += NT) {  // slots of the super-tiles ranked before c: deeper ones, ties by index
-            const uint32_t mine = s_depth[c];
-            uint32_t before = 0;
-            for (int o = 0; o < S; o++) {
-                const uint32_t d = s_depth[o];
-                if (d > mine || (d == mine && o < c)) {
-                    const int ox = o % sgx, oy = o / sgx;
-                    before += (uint32_t)(min(SGR_SUP, j.gx - ox * SGR_SUP) * min(SGR_SUP, j.gy - oy * SGR_SUP));
-                }
-            }
-            s_start[c] = before;
-        }
-        __syncthreads();
-        for (int i = tid; i < T; i += NT) {
-            const int tx = i % j.gx, ty = i / j.gx, sx = tx >> SGR_SUP_SHIFT, sy = ty >> SGR_SUP_SHIFT;
-            const int w = min(SGR_SUP, j.gx - sx * SGR_SUP);
-            const uint32_t slot = s_start[sy * sgx + sx] + (uint32_t)((ty - sy * SGR_SUP) * w + (tx - sx * SGR_SUP));
-            j.order[slot] = (uint32_t)i;
-            if (j.order_copy) j.order_copy[slot] = (uint32_t)i;  // (may alias the forward's tile_order: the blend is done)
-        }
-        return;
-    }
-#endif
     const uint32_t mc = j.header[SGR_HDR_MAXCOUNT];
     const int shift = mc >= 1024u ? (32 - __builtin_clz(mc)) - 10 : 0;  // class = 1023 - (depth >> shift): class 0 = deepest
     for (int c = tid; c < 1024; c += NT) s_cls[c] = 0u;
