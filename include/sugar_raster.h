@@ -734,6 +734,30 @@ int sgr_better_normal_backward(long long N, int K, int P, const float* samples, 
                                int through_normal_only, const float* dL_dloss, float* dL_dnormals, float* dL_dpoints, float* dL_dsamples,
                                char* scratch, void* stream);
 
+/* sgr_projection_loss_*  (coarse_density.py:651-700 with use_projection_as_estimation; csrc/coarse_loss.hip, additive): per sample
+ *   g = sample_idx[n] (int64, wrapped once when negative), est = <x_n - points[g], normals[g]> -- the three products summed left to
+ *   right -- and the terms of sgr_estimation_loss_* over it with the same `mode` and SGR_CL_* flags and the one number `scale` as s:
+ *     mode 0 ('sdf'): | field - |est| | / s or its squared quotient, clamped;  mode 1 ('density'): | field - exp(-0.5 est^2 / beta^2) | or
+ *     its square;  on-surface: |est| / s or (est / s)^2, clamped.
+ *   Every sample is projected: both means divide by N.  A sample whose index is outside [-P, P) contributes nothing, is never
+ *   dereferenced, and still counts in N.  Reduced as the means above: bit-identical from run to run.  scratch:
+ *   sgr_projection_loss_scratch_bytes(N).
+ *   The backward takes the two upstream gradients by DEVICE pointer (NULL = zero) and writes EVERY row of dL_dfield[N], dL_dbeta[N]
+ *   (mode 1), dL_dsamples[N,3] = dest_n n_g, dL_dpoints[P,3] = -n_g sum dest_n and dL_dnormals[P,3] = sum dest_n (x_n - mu_g); each may be
+ *   NULL.  The per-Gaussian sums use no float atomics: the per-sample launch leaves dest_n in the scratch, the samples are grouped by
+ *   Gaussian and one lane per Gaussian adds its samples in ascending sample order (float64 sums); a Gaussian without samples gets zero.  A 'density'
+ *   target that underflowed to 0 passes no gradient (no 0 / 0 at a vanishing beta).  N < 2^32 - 1.  scratch:
+ *   sgr_projection_loss_backward_scratch_bytes(N, P) (0 when N does not fit). */
+size_t sgr_projection_loss_scratch_bytes(long long N);
+int sgr_projection_loss_forward(long long N, int P, int mode, int flags, const float* samples, const int64_t* sample_idx, const float* points,
+                                const float* normals, const float* field, const float* beta, float scale, float clamp_max,
+                                float* loss_estimation, float* loss_surface, char* scratch, void* stream);
+size_t sgr_projection_loss_backward_scratch_bytes(long long N, int P);
+int sgr_projection_loss_backward(long long N, int P, int mode, int flags, const float* samples, const int64_t* sample_idx, const float* points,
+                                 const float* normals, const float* field, const float* beta, float scale, float clamp_max,
+                                 const float* dL_dloss_estimation, const float* dL_dloss_surface, float* dL_dfield, float* dL_dbeta,
+                                 float* dL_dsamples, float* dL_dpoints, float* dL_dnormals, char* scratch, void* stream);
+
 /* sgr_opacity_entropy_*  (coarse_sdf.py:543-551; csrc/coarse_loss.hip, additive): loss = the mean over the rows with visible[p] != 0
  *   (one byte per row) of (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10), o = opacities[P], in that operation order and reduced
  *   as the means above; n_visible[1] (int64) is their count, formed on the device; no visible row gives NaN.  The backward is one

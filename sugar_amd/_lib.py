@@ -109,6 +109,10 @@ SIGNATURES = {
     "sgr_better_normal_forward": (_i, [C.c_longlong, _i, _i] + [_vp] * 10),
     "sgr_better_normal_backward_scratch_bytes": (_sz, [C.c_longlong, _i, _i, _i]),
     "sgr_better_normal_backward": (_i, [C.c_longlong, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 6),
+    "sgr_projection_loss_scratch_bytes": (_sz, [C.c_longlong]),
+    "sgr_projection_loss_forward": (_i, [C.c_longlong, _i, _i, _i] + [_vp] * 6 + [_f, _f] + [_vp] * 4),
+    "sgr_projection_loss_backward_scratch_bytes": (_sz, [C.c_longlong, _i]),
+    "sgr_projection_loss_backward": (_i, [C.c_longlong, _i, _i, _i] + [_vp] * 6 + [_f, _f] + [_vp] * 9),
     "sgr_opacity_entropy_scratch_bytes": (_sz, [_i]),
     "sgr_opacity_entropy_forward": (_i, [_i] + [_vp] * 6),
     "sgr_opacity_entropy_backward": (_i, [_i] + [_vp] * 6),

@@ -1,5 +1,5 @@
 """Host side of the coarse trainers' inline loss terms (csrc/coarse_loss.hip; C ABI: sgr_surface_band, sgr_estimation_loss_*,
-sgr_better_normal_*): the statements that sugar_trainers/coarse_sdf.py:606-716 (and coarse_density.py:610-730) write between the calls
+sgr_projection_loss_*, sgr_better_normal_*): the statements that sugar_trainers/coarse_sdf.py:606-716 (and coarse_density.py:610-730) write between the calls
 of `sample_points_in_gaussians`, `get_field_values` and `get_normals`, as three operations and one composite:
 
     surface_band        the close-to-surface mask of the Gaussians and their view-dependent std                 coarse_sdf.py:610-623
@@ -8,6 +8,9 @@ of `sample_points_in_gaussians`, `get_field_values` and `get_normals`, as three 
     better_normal_loss  the "better normal" mean over the samples                                               :688-716
     regulariser_terms   the whole of :606-716 for any object with SuGaR's attributes                            :606-716
     opacity_entropy     the entropy term the loop adds before the regulariser starts (sgr_opacity_entropy_*)    :543-551
+    projection_estimation_losses   the same two means with est = <x - mu_g, n_g> of the sample's own Gaussian
+                        (`use_projection_as_estimation`, coarse_density.py's default), over every sample        coarse_density.py:651-700
+    density_regulariser_terms      the whole of coarse_density.py:574-730 under that option: no camera, no depth  coarse_density.py:574-730
 
 GPU tensors only; the HIP library must be built.  No operation synchronises with the host; camera matrices (pytorch3d's row vectors)
 and `znear` are read on the device; the depth map is read through its strides.  The scalar means and every per-Gaussian gradient are
@@ -159,6 +162,88 @@ def estimation_losses(samples, depth, world_to_view, projection, znear, *, mode:
     return (est if with_estimation else None), (surf if with_surface else None), M
 
 
+class _ProjectionLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, samples, field, beta, points, normals, sample_idx, mode, flags, scale, clamp_max):
+        x, pts, nrm = _f32c(samples), _f32c(points), _f32c(normals)
+        N, P, dev = x.shape[0], pts.shape[0], x.device
+        f = _f32c(field.reshape(-1)) if field is not None else None
+        b = _f32c(beta.reshape(-1)) if beta is not None else None
+        ix = _idx(sample_idx.reshape(-1))
+        out = torch.zeros(2, device=dev)
+        scratch = _scratch(_lib.load().sgr_projection_loss_scratch_bytes(N), dev)
+        call("sgr_projection_loss_forward", dev, N, P, mode, flags, ptr(x), ptr(ix), ptr(pts), ptr(nrm), ptr(f), ptr(b), scale, clamp_max,
+             ptr(out[0:]) if flags & _WITH_EST else None, ptr(out[1:]) if flags & _WITH_SURFACE else None, ptr(scratch))
+        ctx.save_for_backward(x, f, b, pts, nrm, ix)
+        ctx.consts = (N, P, mode, flags, scale, clamp_max)
+        ctx.shapes = (samples.shape, field.shape if field is not None else None, beta.shape if beta is not None else None)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_est, g_surf):
+        x, f, b, pts, nrm, ix = ctx.saved_tensors
+        N, P, mode, flags, scale, clamp_max = ctx.consts
+        dev = x.device
+        need = ctx.needs_input_grad
+        dx = torch.empty(N, 3, device=dev) if need[0] else None
+        df = torch.empty(N, device=dev) if need[1] and f is not None else None
+        db = torch.empty(N, device=dev) if need[2] and b is not None and mode == 1 else None
+        dp = torch.empty(P, 3, device=dev) if need[3] else None
+        dn = torch.empty(P, 3, device=dev) if need[4] else None
+        if any(t is not None for t in (dx, df, db, dp, dn)):
+            scratch = _scratch(_lib.load().sgr_projection_loss_backward_scratch_bytes(N, P), dev)
+            call("sgr_projection_loss_backward", dev, N, P, mode, flags, ptr(x), ptr(ix), ptr(pts), ptr(nrm), ptr(f), ptr(b), scale, clamp_max,
+                 ptr(_f32c(g_est)), ptr(_f32c(g_surf)), ptr(df), ptr(db), ptr(dx), ptr(dp), ptr(dn), ptr(scratch))
+        s_shape, f_shape, b_shape = ctx.shapes
+        if need[2] and b is not None and db is None:
+            db = torch.zeros(N, device=dev)                                     # mode 'sdf' does not read beta
+        return (dx.reshape(s_shape) if dx is not None else None, df.reshape(f_shape) if df is not None else None,
+                db.reshape(b_shape) if db is not None else None, dp, dn) + (None,) * 5
+
+
+def projection_estimation_losses(samples, sample_idx, points, normals, *, mode: str = "density", sdf=None, density=None, beta=None,
+                                 scale=None, clamp_max: float = float("inf"), with_estimation: bool = True, with_surface: bool = False,
+                                 squared_estimation: bool = False, squared_surface: bool = False):
+    """(estimation, surface) of coarse_density.py:651-700 with `use_projection_as_estimation`: the signed distance estimate of a sample
+    is its offset from its own Gaussian's centre along that Gaussian's normal, `est = <samples - points[sample_idx], normals[sample_idx]>`,
+    every sample counts, and the terms are `estimation_losses`'s: `mode='density'` reads `density[N]` and `beta[N]`, `mode='sdf'` reads
+    `sdf[N]` and the number `scale`; the on-surface term needs `scale` too.  Returns the two means over all N samples as 0-dim device
+    tensors (None for a term that was not asked for).  Differentiable w.r.t. samples, sdf / density, beta, points and normals; the
+    per-Gaussian gradients are summed in a fixed order and every result is bit-identical from run to run.  N < 2^32 - 1."""
+    if mode not in MODES:
+        raise ValueError(f"Unknown sdf_estimation_mode: {mode}")
+    if not (with_estimation or with_surface):
+        raise ValueError("projection_estimation_losses: neither term was asked for")
+    field = (sdf if mode == "sdf" else density) if with_estimation else None
+    b = beta if (with_estimation and mode == "density") else None
+    tensors = dict(samples=samples, sample_idx=sample_idx, points=points, normals=normals)
+    if with_estimation:
+        if field is None or (mode == "density" and b is None):
+            raise ValueError("projection_estimation_losses: mode 'sdf' needs sdf=, mode 'density' needs density= and beta=")
+        tensors["sdf" if mode == "sdf" else "density"] = field
+        if b is not None:
+            tensors["beta"] = b
+    if scale is None and (with_surface or (with_estimation and mode == "sdf")):
+        raise ValueError("projection_estimation_losses: give the samples' scale as scale= (a number)")
+    need_gpu("projection_estimation_losses", **tensors)
+    if samples.dim() != 2 or samples.shape[1] != 3 or samples.shape[0] < 1:
+        raise RuntimeError("projection_estimation_losses: samples must be [N, 3] with N >= 1")
+    N = samples.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1 or normals.shape != points.shape:
+        raise RuntimeError("projection_estimation_losses: expected points[P,3] and normals[P,3] with P >= 1")
+    for name in ("sdf", "density", "beta", "sample_idx"):
+        if name in tensors and tensors[name].numel() != N:
+            raise RuntimeError(f"projection_estimation_losses: {name} must have one entry per sample")
+    if N >= 2 ** 32 - 1:
+        raise RuntimeError("projection_estimation_losses: N must stay below 2^32 - 1")
+    flags = ((_WITH_EST if with_estimation else 0) | (_WITH_SURFACE if with_surface else 0)
+             | (_SQUARED_EST if squared_estimation else 0) | (_SQUARED_SURFACE if squared_surface else 0))
+    est, surf = _ProjectionLosses.apply(_plain(samples), _plain(field) if field is not None else None, _plain(b) if b is not None else None,
+                                        _plain(points), _plain(normals), sample_idx, MODES.index(mode), flags,
+                                        float(scale) if scale is not None else 1.0, float(clamp_max))
+    return (est if with_estimation else None), (surf if with_surface else None)
+
+
 class _BetterNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, samples, normals, points, sample_idx, knn_idx, min_scaling, opacities, only):
@@ -303,4 +388,57 @@ def regulariser_terms(sugar, fov_camera, depth, visibility_filter, *, sdf_estima
         out["sdf_better_normal_loss"] = better_normal_loss(samples, sample_idx, sugar.knn_idx, sugar.get_normals(estimate_from_points=False),
                                                            sugar.points, min_scaling, fields["closest_gaussian_opacities"],
                                                            sdf_better_normal_gradient_through_normal_only)       # :688-716
+    return out
+
+
+def density_regulariser_terms(sugar, visibility_filter, *, sdf_estimation_mode: str = "density", use_sdf_estimation_loss: bool = True,
+                              enforce_samples_to_be_on_surface: bool = False, squared_sdf_estimation_loss: bool = False,
+                              squared_samples_on_surface_loss: bool = False, use_sdf_better_normal_loss: bool = True,
+                              sdf_better_normal_gradient_through_normal_only: bool = True, density_factor: float = 1.0,
+                              density_threshold: float = 1.0, n_samples_for_sdf_regularization: int = 1_000_000,
+                              sdf_sampling_scale_factor: float = 1.5, sdf_sampling_proportional_to_volume: bool = False,
+                              cameras_spatial_extent=None):
+    """coarse_density.py:574-730 for one camera with `use_projection_as_estimation=True` (that trainer's default): the sampling mask
+    is `visibility_filter` alone (the bool [P] `radii > 0`; no band, no depth render, no camera), then
+    `sugar.sample_points_in_gaussians`, `sugar.get_field_values`, `sugar.get_normals`, `projection_estimation_losses` and
+    `better_normal_loss`.  `sugar` is any object with SuGaR's attributes, as for `regulariser_terms`; the options carry the trainer's
+    names and coarse_density.py's defaults (`normalize_by_sdf_std` does not exist here: the reference forces it off, :664-667).
+
+    Returns a dict of the UNWEIGHTED terms as 0-dim device tensors -- 'sdf_estimation_loss', 'samples_on_surface_loss',
+    'sdf_better_normal_loss', each only when asked for -- plus 'n_samples'; the caller applies its factors."""
+    if getattr(sugar, "beta_mode", "average") not in (None, "average"):
+        raise NotImplementedError(f"density_regulariser_terms: beta_mode {sugar.beta_mode!r} is not implemented, only 'average'")
+    if sdf_estimation_mode not in MODES:
+        raise ValueError(f"Unknown sdf_estimation_mode: {sdf_estimation_mode}")
+    estimate = use_sdf_estimation_loss or enforce_samples_to_be_on_surface
+    if not (estimate or use_sdf_better_normal_loss):
+        raise ValueError("density_regulariser_terms: no term was asked for")
+    need_gpu("density_regulariser_terms", points=sugar.points, visibility_filter=visibility_filter)
+    samples, sample_idx = sugar.sample_points_in_gaussians(num_samples=n_samples_for_sdf_regularization,
+                                                           sampling_scale_factor=sdf_sampling_scale_factor, mask=visibility_filter,
+                                                           probabilities_proportional_to_volume=sdf_sampling_proportional_to_volume)   # :634-639
+    fields = sugar.get_field_values(samples, sample_idx,
+                                    return_sdf=estimate and sdf_estimation_mode == "sdf", density_threshold=density_threshold,
+                                    density_factor=density_factor, return_sdf_grad=False, sdf_grad_max_value=10.,
+                                    return_closest_gaussian_opacities=use_sdf_better_normal_loss,
+                                    return_beta=estimate and sdf_estimation_mode == "density")                  # :642-649
+    out = {"n_samples": samples.shape[0]}
+    normals = sugar.get_normals(estimate_from_points=False)
+    if estimate:
+        extent = float(sugar.get_cameras_spatial_extent() if cameras_spatial_extent is None else cameras_spatial_extent)
+        est, surf = projection_estimation_losses(samples, sample_idx, sugar.points, normals, mode=sdf_estimation_mode,
+                                                 sdf=fields.get("sdf"), density=fields.get("density"), beta=fields.get("beta"),
+                                                 scale=extent / 10., clamp_max=10. * extent, with_estimation=use_sdf_estimation_loss,
+                                                 with_surface=enforce_samples_to_be_on_surface,
+                                                 squared_estimation=squared_sdf_estimation_loss,
+                                                 squared_surface=squared_samples_on_surface_loss)               # :651-700
+        if use_sdf_estimation_loss:
+            out["sdf_estimation_loss"] = est
+        if enforce_samples_to_be_on_surface:
+            out["samples_on_surface_loss"] = surf
+    if use_sdf_better_normal_loss:
+        min_scaling = _plain(sugar.scaling).detach().min(dim=-1)[0]                                             # :707
+        out["sdf_better_normal_loss"] = better_normal_loss(samples, sample_idx, sugar.knn_idx, normals, sugar.points, min_scaling,
+                                                           fields["closest_gaussian_opacities"],
+                                                           sdf_better_normal_gradient_through_normal_only)       # :702-730
     return out

@@ -1,5 +1,6 @@
-"""SuGaR's coarse stage with the SDF regulariser as a loop of this package's own: the default schedule of
-sugar_trainers/coarse_sdf.py from a 7 000-iteration 3DGS checkpoint, over `coarse_model.CoarseModel` and the HIP kernels --
+"""SuGaR's coarse stage as a loop of this package's own: the default schedule of sugar_trainers/coarse_sdf.py ("sdf") or of
+sugar_trainers/coarse_density.py ("density") from a 7 000-iteration 3DGS checkpoint, over `coarse_model.CoarseModel` and the HIP
+kernels --
 
     RGB pass      shcolor.sh_to_rgb -> colours, sugar_amd.diff_gaussian_rasterization, fused_loss.l1_ssim_loss        coarse_sdf.py:504-536
     entropy       coarse_loss.opacity_entropy over radii > 0, for 7000 < it < 9000                                    :538-551
@@ -7,17 +8,22 @@ sugar_trainers/coarse_sdf.py from a 7 000-iteration 3DGS checkpoint, over `coars
     prune         strengths < 0.5 at the start of 9001, the Adam moments of the kept rows carried, neighbours reset   :486-497
     SDF pass      for it > 9000: depth rendered as colour (bg = the largest depth, gradient flowing),
                   coarse_loss.regulariser_terms with the draws of coarse_draw, factors 0.2 / 0.2                      :566-716
+    density pass  with regulariser='density' instead of the SDF pass: NO depth render and no band -- the draw over
+                  radii > 0, coarse_loss.density_regulariser_terms (the estimate is the sample's offset along its
+                  own Gaussian's normal, the target exp(-est^2 / 2 beta^2)), factors 0.2 / 0.2            coarse_density.py:570-730
     optimiser     fused_adam.FusedAdam over the reference's six groups and rates, the positions' rate on its schedule sugar_optimizer.py
 
 as a class (`CoarseTrainer.step`) and a command:
 
     python -m sugar_amd.coarse_train POINT_CLOUD.ply --cameras cameras.json --images DIR --out DIR
-        [--iterations 15000 --start-iteration 7000 --estimation-factor 0.2 --normal-factor 0.2 --seed 0]
+        [--regulariser {sdf,density} --iterations 15000 --start-iteration 7000 --estimation-factor 0.2 --normal-factor 0.2 --seed 0]
 
 which writes DIR/<iterations>.pt (the reference's checkpoint shape) and DIR/point_cloud.ply (what `sugar_amd.extract` reads) and
-prints the reference's loss line every 50 iterations.  The schedule is the pure function `phase`.  Not here: coarse_density.py,
-densification inside this loop (the reference's defaults disable it from a trained 3DGS), mesh-bound models, beta modes other than
-'average', `use_projection_as_estimation`, multi-GPU.
+prints the reference's loss line every 50 iterations.  The schedule is the pure function `phase`: the two trainers share it.
+`regulariser='density'` applies DENSITY_OVERRIDES, the four defaults in which coarse_density.py differs; options given by the caller
+win.  Not here: densification inside this loop (the reference's defaults disable it from a trained 3DGS), mesh-bound models, beta
+modes other than 'average', coarse_density.py's depth-map estimate (`use_projection_as_estimation=False` there), the projection
+estimate under the "sdf" regulariser, multi-GPU.
 
 A step reads the device once on top of what the rasterizer's plain API does: the number of Gaussians the draw could choose from,
 once per SDF iteration -- with none, the regulariser is left out of that step, as the reference does (:626, :717-718)."""
@@ -49,7 +55,12 @@ DEFAULTS = dict(
     regularity_knn=16, reset_neighbors_every=500, regularize_from=7000, start_reset_neighbors_from=7001,
     prune_when_starting_regularization=False, prune_low_opacity_gaussians_at=(9000,), prune_hard_opacity_threshold=0.5,
     estimation_factor=0.2, normal_factor=0.2, print_loss_every_n_iterations=50,
+    regulariser="sdf", use_projection_as_estimation=False,
 )
+# what coarse_density.py:112-156 sets differently from coarse_sdf.py (`use_projection_as_estimation` turns the band off, :127-128)
+DENSITY_OVERRIDES = dict(sdf_estimation_mode="density", use_projection_as_estimation=True,
+                         sample_only_in_gaussians_close_to_surface=False, density_factor=1.0)
+REGULARISERS = ("sdf", "density")
 GROUPS = (("points", "_points"), ("sh_coordinates_dc", "_sh_coordinates_dc"), ("sh_coordinates_rest", "_sh_coordinates_rest"),
           ("all_densities", "all_densities"), ("scales", "_scales"), ("quaternions", "_quaternions"))      # sugar_optimizer.py:67-83
 
@@ -113,13 +124,30 @@ class CoarseTrainer:
         unknown = sorted(set(options) - set(DEFAULTS))
         if unknown:
             raise TypeError(f"CoarseTrainer: unknown options {unknown}")
-        self.options = o = dict(DEFAULTS, **options)
+        regulariser = options.get("regulariser", DEFAULTS["regulariser"])
+        if regulariser not in REGULARISERS:
+            raise ValueError(f"CoarseTrainer: regulariser must be one of {REGULARISERS}, got {regulariser!r}")
+        self.options = o = dict(DEFAULTS, **(DENSITY_OVERRIDES if regulariser == "density" else {}))
+        o.update(options)                                                        # the caller's explicit options win
         if not model._points.is_cuda:
             raise RuntimeError("CoarseTrainer: the model must be on a ROCm device; there is no CPU fallback")
         if len({o["start_sdf_regularization_from"], o["start_sdf_estimation_from"], o["start_sdf_better_normal_from"]}) != 1:
             raise NotImplementedError("CoarseTrainer: the regulariser's terms must start together (the reference's default)")
         if not o["backpropagate_gradients_through_depth"]:
             raise NotImplementedError("CoarseTrainer: backpropagate_gradients_through_depth=False is not implemented")
+        if regulariser == "density":
+            if not o["use_projection_as_estimation"]:
+                raise NotImplementedError("CoarseTrainer: regulariser='density' with use_projection_as_estimation=False (the depth-map "
+                                          "estimate of coarse_density.py) is not implemented")
+            if o["sample_only_in_gaussians_close_to_surface"]:
+                raise NotImplementedError("CoarseTrainer: sample_only_in_gaussians_close_to_surface=True with "
+                                          "use_projection_as_estimation=True is not implemented (the reference turns the band off, "
+                                          "coarse_density.py:127-128)")
+            if o["normalize_by_sdf_std"]:
+                raise NotImplementedError("CoarseTrainer: normalize_by_sdf_std=True with use_projection_as_estimation=True is not "
+                                          "implemented (the reference forces it off, coarse_density.py:664-667)")
+        elif o["use_projection_as_estimation"]:
+            raise NotImplementedError("CoarseTrainer: use_projection_as_estimation=True needs regulariser='density'")
         from .fused_adam import FusedAdam
         self.model = model
         if model.cameras is None:
@@ -155,8 +183,32 @@ class CoarseTrainer:
                 group["lr"] = lr
         return lr
 
+    def _density_regulariser(self, ph, visible):
+        """(weighted sum or None, terms) of coarse_density.py:570-730 for one camera: no depth render, the draw over `visible`"""
+        from .coarse_loss import density_regulariser_terms
+        o, model = self.options, self.model
+        terms = density_regulariser_terms(
+            model, visible, sdf_estimation_mode=o["sdf_estimation_mode"],
+            use_sdf_estimation_loss=bool(o["use_sdf_estimation_loss"]) and ph.sdf_estimation,
+            enforce_samples_to_be_on_surface=bool(o["enforce_samples_to_be_on_surface"]) and ph.sdf_estimation,
+            squared_sdf_estimation_loss=o["squared_sdf_estimation_loss"],
+            squared_samples_on_surface_loss=o["squared_samples_on_surface_loss"], use_sdf_better_normal_loss=ph.sdf_better_normal,
+            sdf_better_normal_gradient_through_normal_only=o["sdf_better_normal_gradient_through_normal_only"],
+            density_factor=o["density_factor"], density_threshold=o["density_threshold"],
+            n_samples_for_sdf_regularization=o["n_samples_for_sdf_regularization"],
+            sdf_sampling_scale_factor=o["sdf_sampling_scale_factor"],
+            sdf_sampling_proportional_to_volume=o["sdf_sampling_proportional_to_volume"], cameras_spatial_extent=self.extent)
+        self.n_masked = int(model.last_draw[2])          # the step's one host read, after the terms, as in `_regulariser`
+        if self.n_masked == 0:
+            return None, {}                                                                                              # :632-633, :731-732
+        weights = dict(sdf_estimation_loss=o["estimation_factor"], samples_on_surface_loss=o["samples_on_surface_factor"],
+                       sdf_better_normal_loss=o["normal_factor"])
+        return sum(weights[k] * terms[k] for k in weights if k in terms), terms
+
     def _regulariser(self, ph, camera_index, visible):
         """(weighted sum or None, terms) of :566-716 for one camera"""
+        if self.options["regulariser"] == "density":
+            return self._density_regulariser(ph, visible)
         from .coarse_loss import regulariser_terms
         o, model = self.options, self.model
         fov_camera = model.p3d_cameras[camera_index]
@@ -265,7 +317,8 @@ def _find_image(directory, name):
 
 def _parser():
     ap = argparse.ArgumentParser(prog="python -m sugar_amd.coarse_train", description="SuGaR's coarse stage with the SDF regulariser "
-                                 "(coarse_sdf.py's default schedule) from a trained 3DGS point cloud, on the HIP kernels")
+                                 "(coarse_sdf.py's default schedule) or the density regulariser (coarse_density.py's) from a trained "
+                                 "3DGS point cloud, on the HIP kernels")
     ap.add_argument("point_cloud", help="the 3DGS checkpoint's point_cloud.ply")
     ap.add_argument("--cameras", required=True, help="cameras.json (the 3DGS format)")
     ap.add_argument("--images", required=True, help="directory of the training images, named like the cameras")
@@ -277,6 +330,8 @@ def _parser():
     ap.add_argument("--samples", type=int, default=DEFAULTS["n_samples_for_sdf_regularization"], help="samples of the regulariser per iteration")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--regulariser", choices=REGULARISERS, default=DEFAULTS["regulariser"],
+                    help="sdf: coarse_sdf.py's loop; density: coarse_density.py's (recommended for object-centric scenes)")
     return ap
 
 
@@ -300,7 +355,7 @@ def main(argv=None) -> int:
         images.append(rgb)
     model = CoarseModel.from_gaussian_ply(a.point_cloud, cams, device=dev, seed=a.seed)
     trainer = CoarseTrainer(model, cams, images, num_iterations=a.iterations, estimation_factor=a.estimation_factor,
-                            normal_factor=a.normal_factor, n_samples_for_sdf_regularization=a.samples)
+                            normal_factor=a.normal_factor, n_samples_for_sdf_regularization=a.samples, regulariser=a.regulariser)
     print(f"{model.n_points} Gaussians, {len(cams)} cameras, spatial extent {trainer.extent:.4g}; "
           f"iterations {a.start_iteration + 1} .. {a.iterations}")
     iteration, epoch = trainer.run(a.start_iteration, a.iterations, seed=a.seed)

@@ -14,6 +14,9 @@
 //                       w^ = w / max(sum_k w, 1e-6) (the sum detached),  loss_n = | n_s - sum_k w^_k c_k |^2, averaged over N.
 //                       K = 16: one lane per (sample, neighbour) pair, the sixteen pairs of a sample in one DPP row; any other K: one
 //                       lane per sample.
+//   projection losses : coarse_density.py:651-700 with use_projection_as_estimation (sgr_projection_loss_*).  One lane per sample:
+//                       g = sample_idx[n], est = <x - mu_g, n_g> (three products, summed left to right), every sample counts (the
+//                       divisor is N), then the 'sdf' / 'density' / on-surface terms above with the one number s as the scale.
 //   opacity entropy   : :543-551, the term the loop adds before the regulariser starts.  One lane per Gaussian:
 //                       (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10), averaged over the visible rows; their count is formed on
 //                       the device, no visible row gives NaN.  The backward writes every row, zero where invisible.
@@ -22,6 +25,10 @@
 // divides: no float atomics, the same bits every run.  Per-Gaussian gradients of the better-normal loss: every (sample, neighbour)
 // pair and every sample's own Gaussian writes one row of a table, the N (K + 1) rows are grouped by Gaussian (group.hip) and sixteen
 // lanes per Gaussian fold them with row rotates -- every row of the output is written, zero where nothing references the Gaussian.
+// Per-Gaussian gradients of the projection losses: the per-sample pass leaves only dL/dest_n behind (4 B per sample), the samples are
+// grouped by their Gaussian (group.hip, the int64 indices as they are) and ONE lane per Gaussian folds its samples in ascending sample
+// order (float64 sums), re-reading x_n:  dL/dmu_g = -n_g sum dest_n,  dL/dn_g = sum dest_n (x_n - mu_g).  No row table: the draw is uniform over the
+// Gaussians in view, a few samples each, and a table would write and read back 24 B per sample for what 16 B of gathers give.
 // The one output that is NOT reproducible bit for bit is the depth map's gradient of the estimation backward: four float atomic adds
 // per sample, as sgr_depth_lookup_backward.
 //
@@ -436,6 +443,154 @@ __global__ void __launch_bounds__(256) k_normal_rows_gather(int P, const float* 
     }
 }
 
+// -------------------------------------------------------------------------------------------------------- projection losses
+struct ProjArgs {
+    long long N; int P, flags;
+    const float* x; const long long* idx;            // samples[N,3], sample_idx[N]
+    const float *points, *normals;                   // [P,3], [P,3]
+    const float *field, *beta;                       // sdf[N] ('sdf') or density[N] ('density'); beta[N] ('density' only)
+    float s, cmax;
+};
+
+struct ProjSample { bool ok; float n0, n1, n2, est; };
+
+// est = <x - mu_g, n_g> of coarse_density.py:655-656; a sample whose index is outside [-P, P) is left out, never dereferenced
+__device__ __forceinline__ ProjSample proj_sample(const ProjArgs& a, long long n)
+{
+    ProjSample e;
+    const long long i = wrap_row(a.idx[n], a.P);
+    e.ok = i >= 0 && i < a.P;
+    e.n0 = e.n1 = e.n2 = e.est = 0.f;
+    if (e.ok) {
+        e.n0 = a.normals[3 * i]; e.n1 = a.normals[3 * i + 1]; e.n2 = a.normals[3 * i + 2];
+        const float d0 = a.x[3 * n] - a.points[3 * i], d1 = a.x[3 * n + 1] - a.points[3 * i + 1], d2 = a.x[3 * n + 2] - a.points[3 * i + 2];
+        e.est = (d0 * e.n0 + d1 * e.n1) + d2 * e.n2;
+    }
+    return e;
+}
+
+template <bool DENSITY>
+__global__ void __launch_bounds__(256) k_projection_fwd(ProjArgs a, double* __restrict__ partial, size_t n_blocks)
+{
+    __shared__ double s_wave[4];
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    double t_est = 0.0, t_surf = 0.0;
+    if (n < a.N) {
+        const ProjSample e = proj_sample(a, n);
+        if (e.ok) {
+            if (a.flags & CL_WITH_EST) {
+                float v;
+                if constexpr (DENSITY) {
+                    const float b = a.beta[n];
+                    const float d = a.field[n] - expf((-0.5f * (e.est * e.est)) / (b * b));
+                    v = (a.flags & CL_SQUARED_EST) ? d * d : fabsf(d);
+                } else {
+                    const float t = a.field[n] - fabsf(e.est);
+                    if (a.flags & CL_SQUARED_EST) { const float u = t / a.s; v = u * u; } else v = fabsf(t) / a.s;
+                    v = clamp_max(v, a.cmax);
+                }
+                t_est = (double)v;
+            }
+            if (a.flags & CL_WITH_SURFACE) {
+                float v;
+                if (a.flags & CL_SQUARED_SURFACE) { const float u = e.est / a.s; v = u * u; } else v = fabsf(e.est) / a.s;
+                t_surf = (double)clamp_max(v, a.cmax);
+            }
+        }
+    }
+    t_est = block_sum256(t_est, s_wave);
+    t_surf = block_sum256(t_surf, s_wave);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = t_est; partial[n_blocks + blockIdx.x] = t_surf; }
+}
+
+// the per-sample pass: dfield, dbeta, dsamples = dest n_g, and dest itself for the fold
+template <bool DENSITY>
+__global__ void __launch_bounds__(256) k_projection_bwd(ProjArgs a, const float* __restrict__ g_est, const float* __restrict__ g_surf,
+                                                        float* __restrict__ dfield, float* __restrict__ dbeta, float* __restrict__ dx,
+                                                        float* __restrict__ dest_out)
+{
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.N) return;
+    const ProjSample e = proj_sample(a, n);
+    float df = 0.f, db = 0.f, dest = 0.f;
+    if (e.ok) {
+        const float Nf = (float)a.N;
+        if ((a.flags & CL_WITH_EST) && g_est) {
+            const float gm = g_est[0] / Nf;                                     // mean
+            if constexpr (DENSITY) {
+                const float b = a.beta[n];
+                const float num = -0.5f * (e.est * e.est), den = b * b;
+                const float T = expf(num / den);
+                const float d = a.field[n] - T;
+                df = (a.flags & CL_SQUARED_EST) ? gm * (2.f * d) : gm * sgnf(d);
+                const float da = -df * T;                                       // through exp
+                if (da != 0.f) {                                                // (a target that underflowed passes nothing: no 0 / 0 at a tiny beta)
+                    dest += (da / den) * (-0.5f) * (2.f * e.est);
+                    db = (-da * num / (den * den)) * (2.f * b);
+                }
+            } else {
+                const float t = a.field[n] - fabsf(e.est);
+                if (a.flags & CL_SQUARED_EST) {
+                    const float u = t / a.s;
+                    df = (u * u <= a.cmax) ? (gm * (2.f * u)) / a.s : 0.f;
+                } else {
+                    df = (fabsf(t) / a.s <= a.cmax) ? (gm / a.s) * sgnf(t) : 0.f;
+                }
+                dest -= df * sgnf(e.est);
+            }
+        }
+        if ((a.flags & CL_WITH_SURFACE) && g_surf) {
+            const float gm = g_surf[0] / Nf;
+            if (a.flags & CL_SQUARED_SURFACE) {
+                const float u = e.est / a.s;
+                if (u * u <= a.cmax) dest += (gm * (2.f * u)) / a.s;
+            } else if (fabsf(e.est) / a.s <= a.cmax) {
+                dest += (gm / a.s) * sgnf(e.est);
+            }
+        }
+    }
+    if (dfield) dfield[n] = df;
+    if (DENSITY && dbeta) dbeta[n] = db;
+    if (dx) { dx[3 * n] = dest * e.n0; dx[3 * n + 1] = dest * e.n1; dx[3 * n + 2] = dest * e.n2; }
+    if (dest_out) dest_out[n] = dest;
+}
+
+// ONE lane per Gaussian folds its samples in ascending sample order; every row is written
+__global__ void __launch_bounds__(256) k_projection_fold(int P, const float* __restrict__ x, const float* __restrict__ points,
+                                                         const float* __restrict__ normals, const float* __restrict__ dest,
+                                                         const uint32_t* __restrict__ start, const uint32_t* __restrict__ list,
+                                                         float* __restrict__ dpoints, float* __restrict__ dnormals)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= P) return;
+    const uint32_t e0 = start[t], e1 = start[t + 1];
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, m0 = 0.f, m1 = 0.f, m2 = 0.f;
+    if (e1 > e0) {
+        // float64 sums: the signed dest_n of one Gaussian cancel (samples on either side of its plane), and a float32 running sum would
+        // lose against the per-sample values what the cancellation amplifies; the adds are few and the pass is bound by its gathers
+        const float u0 = points[3 * t], u1 = points[3 * t + 1], u2 = points[3 * t + 2];
+        double S = 0.0, A0 = 0.0, A1 = 0.0, A2 = 0.0;
+        for (uint32_t e = e0; e < e1; e++) {
+            const size_t n = list[e];
+            const double d = (double)dest[n];
+            S += d;
+            A0 += d * (double)(x[3 * n] - u0); A1 += d * (double)(x[3 * n + 1] - u1); A2 += d * (double)(x[3 * n + 2] - u2);
+        }
+        a0 = (float)A0; a1 = (float)A1; a2 = (float)A2;
+        m0 = (float)(-((double)normals[3 * t] * S)); m1 = (float)(-((double)normals[3 * t + 1] * S));
+        m2 = (float)(-((double)normals[3 * t + 2] * S));
+    }
+    if (dpoints) { dpoints[3 * t] = m0; dpoints[3 * t + 1] = m1; dpoints[3 * t + 2] = m2; }
+    if (dnormals) { dnormals[3 * t] = a0; dnormals[3 * t + 1] = a1; dnormals[3 * t + 2] = a2; }
+}
+
+bool proj_args_ok(const ProjArgs& a, int mode)
+{
+    return a.N > 0 && (unsigned long long)a.N < 0xFFFFFFFFull && a.P > 0 && (mode == 0 || mode == 1) && a.x && a.idx && a.points &&
+           a.normals && (!(a.flags & CL_WITH_EST) || (a.field && (mode == 0 || a.beta))) && (a.flags & (CL_WITH_EST | CL_WITH_SURFACE)) &&
+           !(a.flags & ~15);
+}
+
 // ---------------------------------------------------------------------------------------------------------- opacity entropy
 // coarse_sdf.py:548-551 for one row, in the trainer's operation order: (-o) log(o + 1e-10) - (1 - o) log((1 - o) + 1e-10)
 __global__ void __launch_bounds__(256) k_entropy_fwd(int P, const float* __restrict__ opac, const uint8_t* __restrict__ visible,
@@ -536,6 +691,59 @@ int sgr_estimation_loss_backward(long long N, int P, int mode, int flags, const 
     else
         hipLaunchKernelGGL(k_estimation_bwd<false>, dim3(blocks256((size_t)N)), dim3(256), 0, s, a, M, dL_dloss_estimation, dL_dloss_surface,
                            dL_dfield, dL_dbeta, dL_dsamples, dL_ddepth);
+    return sgr_launch_status();
+}
+
+size_t sgr_projection_loss_scratch_bytes(long long N) { return cl_projection_fwd_scratch_bytes(N); }
+
+int sgr_projection_loss_forward(long long N, int P, int mode, int flags, const float* samples, const int64_t* sample_idx, const float* points,
+                                const float* normals, const float* field, const float* beta, float scale, float clamp_max,
+                                float* loss_estimation, float* loss_surface, char* scratch, void* stream)
+{
+    const ProjArgs a{N, P, flags, samples, reinterpret_cast<const long long*>(sample_idx), points, normals, field, beta, scale, clamp_max};
+    if (!proj_args_ok(a, mode) || !scratch || ((flags & CL_WITH_EST) && !loss_estimation) || ((flags & CL_WITH_SURFACE) && !loss_surface))
+        return SGR_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = cl_estimation_blocks(N);
+    double* partial = reinterpret_cast<double*>(scratch);
+    if (mode == 1) hipLaunchKernelGGL(k_projection_fwd<true>, dim3((unsigned)nb), dim3(256), 0, s, a, partial, nb);
+    else hipLaunchKernelGGL(k_projection_fwd<false>, dim3((unsigned)nb), dim3(256), 0, s, a, partial, nb);
+    hipLaunchKernelGGL(k_finish_means, dim3(1), dim3(256), 0, s, partial, nb, 2, -1, (double)N, (flags & CL_WITH_EST) ? loss_estimation : nullptr,
+                       (flags & CL_WITH_SURFACE) ? loss_surface : nullptr, nullptr);
+    return sgr_launch_status();
+}
+
+size_t sgr_projection_loss_backward_scratch_bytes(long long N, int P)
+{
+    if (N <= 0 || (unsigned long long)N >= 0xFFFFFFFFull) return 0;
+    return cl_projection_bwd_layout((size_t)N, P, sgr_group_scratch_bytes((size_t)N)).total;
+}
+
+int sgr_projection_loss_backward(long long N, int P, int mode, int flags, const float* samples, const int64_t* sample_idx, const float* points,
+                                 const float* normals, const float* field, const float* beta, float scale, float clamp_max,
+                                 const float* dL_dloss_estimation, const float* dL_dloss_surface, float* dL_dfield, float* dL_dbeta,
+                                 float* dL_dsamples, float* dL_dpoints, float* dL_dnormals, char* scratch, void* stream)
+{
+    const ProjArgs a{N, P, flags, samples, reinterpret_cast<const long long*>(sample_idx), points, normals, field, beta, scale, clamp_max};
+    if (!proj_args_ok(a, mode) || !scratch) return SGR_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const ClProjectionBwdLayout L = cl_projection_bwd_layout((size_t)N, P, sgr_group_scratch_bytes((size_t)N));
+    const bool fold = dL_dpoints || dL_dnormals;
+    float* dest = fold ? reinterpret_cast<float*>(scratch + L.dest) : nullptr;
+    if (mode == 1)
+        hipLaunchKernelGGL(k_projection_bwd<true>, dim3(blocks256((size_t)N)), dim3(256), 0, s, a, dL_dloss_estimation, dL_dloss_surface,
+                           dL_dfield, dL_dbeta, dL_dsamples, dest);
+    else
+        hipLaunchKernelGGL(k_projection_bwd<false>, dim3(blocks256((size_t)N)), dim3(256), 0, s, a, dL_dloss_estimation, dL_dloss_surface,
+                           dL_dfield, dL_dbeta, dL_dsamples, dest);
+    if (fold) {
+        uint32_t* start = reinterpret_cast<uint32_t*>(scratch + L.start);
+        const uint32_t* list = nullptr;
+        const int rc = sgr_group_by_key(N, a.idx, P, scratch + L.group, start, &list, s);
+        if (rc < 0) return rc;
+        hipLaunchKernelGGL(k_projection_fold, dim3(blocks256((size_t)P)), dim3(256), 0, s, P, samples, points, normals, dest, start, list,
+                           dL_dpoints, dL_dnormals);
+    }
     return sgr_launch_status();
 }
 

@@ -5,6 +5,8 @@
 //   better-normal fwd   : partial f64[blocks]                                 (blocks = ceil(N / 16) at K = 16, ceil(N / 256) otherwise)
 //   better-normal bwd   : keys i64[E] | start u32[P + 1] | rows f32[E][W] | the grouping's scratch for E entries
 //                         E = N * (K + 1) entries (the pairs, then each sample's own Gaussian), W = 3 (normals) or 6 (+ points)
+//   projection forward  : partial f64[2][ceil(N / 256)]                       (estimation term | on-surface term)
+//   projection backward : dest f32[N] | start u32[P + 1] | the grouping's scratch for N entries
 // Every part starts 256-byte aligned.
 #pragma once
 #include <stddef.h>
@@ -41,6 +43,21 @@ static inline ClNormalBwdLayout cl_normal_bwd_layout(size_t entries, int P, int 
     L.keys = off;  off = cl_align(off + entries * sizeof(int64_t));
     L.start = off; off = cl_align(off + ((size_t)(P > 0 ? P : 0) + 1) * sizeof(uint32_t));
     L.rows = off;  off = cl_align(off + entries * (size_t)width * sizeof(float));
+    L.group = off; off = cl_align(off + group_bytes);
+    L.total = off;
+    return L;
+}
+
+static inline size_t cl_projection_fwd_scratch_bytes(long long N) { return cl_align(2 * cl_estimation_blocks(N) * sizeof(double)); }
+
+struct ClProjectionBwdLayout { size_t dest, start, group, total; };
+// group_bytes: sgr_group_scratch_bytes(N)
+static inline ClProjectionBwdLayout cl_projection_bwd_layout(size_t N, int P, size_t group_bytes)
+{
+    ClProjectionBwdLayout L;
+    size_t off = 0;
+    L.dest = off;  off = cl_align(off + N * sizeof(float));
+    L.start = off; off = cl_align(off + ((size_t)(P > 0 ? P : 0) + 1) * sizeof(uint32_t));
     L.group = off; off = cl_align(off + group_bytes);
     L.total = off;
     return L;
