@@ -332,13 +332,18 @@ int sgr_sh_adam_from_views_ex(int P, int n_views, int D, int M, const float* mea
 int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
                           float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
                           const uint32_t* guard_header, uint32_t guard_capacity, void* stream);
+/* The same update by n_adam persistent one-wave workgroups (a multiple of 8 in [8, 65536]), each over every n_adam-th block of 64
+ * Gaussians with its loads pipelined: the form that rides in the blend backward's launch, as a launch of its own.  Same bits. */
+int sgr_sh_adam_zero_grad_persistent(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                                     float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                                     const uint32_t* guard_header, uint32_t guard_capacity, int n_adam, void* stream);
 int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
                                   const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq,
                                   float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
                                   uint8_t* reach, const uint32_t* guard_header, uint32_t guard_capacity, void* stream);
-/* Process-wide switch of the train step (sgr_trainer_step with all four phases, one view, M == 16): the zero-gradient half runs as extra
- * workgroups inside the blend backward's launch, the masked half in the optimiser's place.  SGR_ADAM_OVERLAP=0 / 1 in the environment
- * sets the default; SGR_ADAM_OVERLAP_K the Adam workgroups behind every 32 blend workgroups (a multiple of 8, default 24).
+/* Process-wide switch of the train step (sgr_trainer_step with all four phases, one view, M == 16): the zero-gradient half runs as
+ * persistent workgroups inside the blend backward's launch, the masked half in the optimiser's place.  SGR_ADAM_OVERLAP=0 / 1 in the
+ * environment sets the default; SGR_ADAM_OVERLAP_WAVES the number of those workgroups (a multiple of 8, default 512).
  * 2 is a verification mode: the forward sets the flags, the dense kernel runs and nothing clears them. */
 void sgr_set_adam_overlap(int on);
 int sgr_get_adam_overlap(void);

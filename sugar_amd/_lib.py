@@ -52,6 +52,7 @@ SIGNATURES = {
     "sgr_sh_adam_from_views": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp]),
     "sgr_sh_adam_from_views_ex": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "sgr_sh_adam_zero_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, C.c_uint32, _vp]),
+    "sgr_sh_adam_zero_grad_persistent": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, C.c_uint32, _i, _vp]),
     "sgr_sh_adam_from_views_masked": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _f, _vp, _vp,
                                            C.c_uint32, _vp]),
     "sgr_set_adam_overlap": (None, [_i]),

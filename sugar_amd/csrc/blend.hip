@@ -763,23 +763,14 @@ blend_bwd_body(int W, int H, int gx, int T_tiles, const uint32_t* __restrict__ t
 {
     __shared__ __attribute__((aligned(16))) float s_q[(BW_QCAP + 1) * BW_ENTRY_DW];  // (+1: phase A's look-ahead)
     int wg = blockIdx.x;
-    // The ride-along (sh_adam_update.h): with a job the grid is [ n_with x (32 blend workgroups, k Adam workgroups) | the other blend
-    // groups | the Adam workgroups left over ].  This kernel leaves HBM nearly idle and the zero-gradient Adam of the Gaussians the
-    // forward never flagged is pure streaming that waits for nothing the backward computes.  k is a multiple of 8, so a blend workgroup
-    // keeps its XCD (sgr_slot_of_workgroup).  Wave-uniform: blockIdx and kernel arguments only.
+    // The ride-along (sh_adam_update.h): with a job the grid is [ n_adam persistent Adam workgroups | the blend workgroups ].  This
+    // kernel leaves HBM nearly idle and the zero-gradient Adam of the Gaussians the forward never flagged is pure streaming that waits
+    // for nothing the backward computes.  The Adam workgroups are dispatched first, split the 64-Gaussian blocks among themselves
+    // statically and live for most of the launch.  n_adam is a multiple of 8, so a blend workgroup keeps its XCD
+    // (sgr_slot_of_workgroup).  Wave-uniform: blockIdx and kernel arguments only.
     if (job.P > 0) {
-        const int per = 32 + job.k, n1 = job.n_with * per;
-        int adam = -1;
-        if (wg < n1) {
-            const int q = wg / per, r = wg - q * per;
-            if (r < 32) wg = q * 32 + r; else adam = q * job.k + (r - 32);
-        } else {
-            const int w2 = wg - n1, rest = (job.n_groups - job.n_with) * 32;
-            if (w2 < rest) wg = job.n_with * 32 + w2; else adam = job.n_with * job.k + (w2 - rest);
-        }
-        // (four float4 steps per round of loads, as in k_sh_adam_from_views: six cost the kernel a wave per SIMD -- 110 VGPRs --, two
-        // changed nothing, and neither did s_setprio 1 for the blend waves: profiles/adam_overlap_ab.txt)
-        if (adam >= 0) { sgr_sh_adam_zero_wave<4>(job, adam * 64); return; }
+        if (wg < job.n_adam) { sgr_sh_adam_zero_persistent(job, wg, job.n_adam); return; }
+        wg -= job.n_adam;
     }
     if (SGR_FORWARD_INVALID(header, list_cap)) return;  // the forward was a no-op (blk_nb, masks, lists are not there)
     __shared__ float2 s_zw[BW_SUB * BW_ZW_STRIDE];
@@ -1087,12 +1078,11 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
     const int T = gx * gy;
     SgrShAdamJob job = {};
     unsigned grid = sgr_blend_grid(T);
-    if (job_in && job_in->P > 0 && job_in->k >= 8 && (job_in->k & 7) == 0) {
+    if (job_in && job_in->P > 0 && job_in->n_adam >= 8 && (job_in->n_adam & 7) == 0) {
         job = *job_in;
-        const int n_adam = (job.P + 63) / 64;
-        job.n_groups = (int)(grid / 32u);
-        job.n_with = n_adam / job.k < job.n_groups ? n_adam / job.k : job.n_groups;
-        grid += (unsigned)n_adam;
+        const int n_blocks = (job.P + 63) / 64;  // (no more persistent workgroups than blocks, still a multiple of 8)
+        if (job.n_adam > n_blocks) job.n_adam = (n_blocks + 7) & ~7;
+        grid += (unsigned)job.n_adam;
     }
     if (order_ready) {}                           // (the forward sorted: sgr_forward_opts.tile_order_out)
     else if (4 * T < 8192) tile_order = nullptr;  // (fewer waves than the chip holds at once: nothing to order)
@@ -1102,6 +1092,6 @@ void sgr_launch_blend_bwd(int W, int H, int gx, int gy, const uint32_t* tile_sta
     }
     hipLaunchKernelGGL(exact ? k_blend_bwd_wx : k_blend_bwd_w, dim3(grid), dim3(64), 0, s, W, H, gx, T, tile_start, point_list, binning, blk_nb, rec,
                        bg, final_T, n_contrib, dL_dpix, acc, tile_order, header, list_cap, job);
-    // (a job this launch could not carry -- k no multiple of 8 -- is still done: a launch of its own)
+    // (a job this launch could not carry -- n_adam no multiple of 8 -- is still done: a launch of its own)
     if (job_in && job_in->P > 0 && job.P == 0) sgr_launch_sh_adam_zero(*job_in, s);
 }

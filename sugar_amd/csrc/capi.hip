@@ -138,18 +138,18 @@ uint32_t sgr_deep_min()
 }
 
 // SH-Adam of unreached Gaussians inside the blend backward's launch (include/sugar_raster.h: sgr_set_adam_overlap); SGR_ADAM_OVERLAP
-// in the environment sets the default, SGR_ADAM_OVERLAP_K the Adam workgroups behind every 32 blend workgroups (a multiple of 8)
+// in the environment sets the default, SGR_ADAM_OVERLAP_WAVES the persistent Adam workgroups in front of the blend's (a multiple of 8)
 static int g_adam_overlap = -1;
 int sgr_adam_overlap()
 {
     if (g_adam_overlap < 0) { const char* e = getenv("SGR_ADAM_OVERLAP"); g_adam_overlap = e ? (e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0)) : SGR_ADAM_OVERLAP_DEFAULT; }
     return g_adam_overlap;
 }
-int sgr_adam_overlap_k()
+int sgr_adam_overlap_waves()
 {
-    static int k = -1;
-    if (k < 0) { const char* e = getenv("SGR_ADAM_OVERLAP_K"); k = e ? atoi(e) : 24; if (k < 8 || (k & 7)) k = 24; }
-    return k;
+    const char* e = getenv("SGR_ADAM_OVERLAP_WAVES");  // (read per step: one getenv, and a test or an A/B run can change it in-process)
+    const int n = e ? atoi(e) : SGR_ADAM_OVERLAP_WAVES_DEFAULT;
+    return (n < 8 || (n & 7) || n > 65536) ? SGR_ADAM_OVERLAP_WAVES_DEFAULT : n;
 }
 // Backward preprocess of the train step by reach flag (include/sugar_raster.h: sgr_set_rows_by_reach); SGR_ROWS_BY_REACH=0 / 1 in the
 // environment sets the default (on)
@@ -740,9 +740,10 @@ static bool sh_split_ok(int M, const float* sh, const float* m, const float* v)
     return M == 16 && ((((uintptr_t)sh | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
 }
 
-int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
-                          float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
-                          uint32_t guard_capacity, void* stream)
+// (n_adam == 0: one wave per 64 Gaussians; otherwise that many persistent waves)
+static int sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                             float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
+                             uint32_t guard_capacity, int n_adam, void* stream)
 {
     if (P <= 0) return 0;
     if (step < 1 || !sh_params || !exp_avg || !exp_avg_sq || !reach) return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad: bad argument");
@@ -753,10 +754,30 @@ int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float*
     job.lr_dc = lr_dc; job.lr_rest = lr_rest; job.b1 = beta1; job.b2 = beta2; job.omb1 = sgr_one_minus(beta1); job.omb2 = sgr_one_minus(beta2);
     job.eps = eps; job.grad_scale = grad_scale; job.zero = 0.f; job.guard = guard_header; job.guard_cap = guard_capacity;
     sgr_bias_corrections(beta1, beta2, step, &job.bc1, &job.bc2_sqrt);
-    sgr_launch_sh_adam_zero(job, (hipStream_t)stream);
+    job.n_adam = n_adam;
+    if (n_adam > 0) sgr_launch_sh_adam_zero_persistent(job, (hipStream_t)stream);
+    else sgr_launch_sh_adam_zero(job, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_zero_grad: ") + hipGetErrorString(e));
     return 0;
+}
+
+int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                          float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
+                          uint32_t guard_capacity, void* stream)
+{
+    return sh_adam_zero_grad(P, M, sh_params, exp_avg, exp_avg_sq, reach, lr_dc, lr_rest, beta1, beta2, eps, step, grad_scale, guard_header,
+                             guard_capacity, 0, stream);
+}
+
+int sgr_sh_adam_zero_grad_persistent(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
+                                     float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                                     const uint32_t* guard_header, uint32_t guard_capacity, int n_adam, void* stream)
+{
+    if (n_adam < 8 || (n_adam & 7) || n_adam > 65536)
+        return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad_persistent: n_adam must be a multiple of 8 in [8, 65536]");
+    return sh_adam_zero_grad(P, M, sh_params, exp_avg, exp_avg_sq, reach, lr_dc, lr_rest, beta1, beta2, eps, step, grad_scale, guard_header,
+                             guard_capacity, n_adam, stream);
 }
 
 int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,

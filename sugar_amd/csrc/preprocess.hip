@@ -1284,8 +1284,10 @@ __global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, 
     if (MASKED && idx < P) a.reach[idx] = 0;
 }
 
-// the zero-gradient half as a launch of its own: one wave per 64 Gaussians (the same body rides in k_blend_bwd_w / _wx)
+// the zero-gradient half as a launch of its own, one wave per 64 Gaussians: for a step with no blend backward to ride in
 __global__ void __launch_bounds__(64) k_sh_adam_zero(SgrShAdamJob job) { sgr_sh_adam_zero_wave<4>(job, (int)blockIdx.x * 64); }
+// ... and the persistent form the blend backward carries, as a launch of its own: job.n_adam waves, each over every n_adam-th block
+__global__ void __launch_bounds__(64) k_sh_adam_zero_persistent(SgrShAdamJob job) { sgr_sh_adam_zero_persistent(job, (int)blockIdx.x, job.n_adam); }
 
 // ---------------------------------------------------------------------------------------------
 // SuGaR.get_points_rgb (sugar_scene/sugar_model.py:839-883): colours = clamp_min(eval_sh(levels-1, sh, dir) + 0.5, 0) with
@@ -1457,6 +1459,12 @@ void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s)
 {
     if (job.P <= 0) return;
     hipLaunchKernelGGL(k_sh_adam_zero, dim3((job.P + 63) / 64), dim3(64), 0, s, job);
+}
+
+void sgr_launch_sh_adam_zero_persistent(const SgrShAdamJob& job, hipStream_t s)
+{
+    if (job.P <= 0 || job.n_adam <= 0) return;
+    hipLaunchKernelGGL(k_sh_adam_zero_persistent, dim3(job.n_adam), dim3(64), 0, s, job);
 }
 
 void sgr_launch_sh_grad_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,

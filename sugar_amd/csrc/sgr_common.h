@@ -219,12 +219,12 @@ void sgr_launch_sh_adam_from_views(int P, int V, int D, int M, size_t vstride, c
                                    float eps, float bc1, float bc2_sqrt, float grad_scale, float* dmean_extra, hipStream_t s,
                                    const uint32_t* guard = nullptr, uint32_t guard_cap = 0, uint8_t* reach = nullptr);
 // The other half of the masked mode: the Adam update with a gradient of zero for the rows whose reach flag is 0 (sh_adam_update.h).
-// As a job it rides in the blend backward's launch as extra workgroups (sgr_launch_blend_bwd); sgr_launch_sh_adam_zero is the same
-// body as a launch of its own.
+// As a job it rides in the blend backward's launch as n_adam persistent workgroups in front of the blend's (sgr_launch_blend_bwd);
+// sgr_launch_sh_adam_zero is a launch of its own with one wave per 64 Gaussians, sgr_launch_sh_adam_zero_persistent the persistent
+// form as a launch of its own.
 struct SgrShAdamJob {
     int P;                       // Gaussians; 0 = no job
-    int k;                       // Adam workgroups behind every group of 32 blend workgroups (a multiple of 8)
-    int n_groups, n_with;        // set by sgr_launch_blend_bwd: groups of 32 blend workgroups, and how many of them carry k Adam workgroups
+    int n_adam;                  // persistent Adam workgroups of the ride-along (a multiple of 8)
     float* sh; float* exp_avg; float* exp_avg_sq;   // [P][48], 16-byte aligned
     const uint8_t* reach;        // [P]
     float lr_dc, lr_rest, b1, b2, omb1, omb2, eps, bc1, bc2_sqrt, grad_scale;
@@ -232,10 +232,12 @@ struct SgrShAdamJob {
     const uint32_t* guard; uint32_t guard_cap;  // as ShAdamArgs: forward header + list capacity (NULL: no check)
 };
 void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s);
+void sgr_launch_sh_adam_zero_persistent(const SgrShAdamJob& job, hipStream_t s);  // job.n_adam one-wave workgroups
 #define SGR_ADAM_OVERLAP_DEFAULT 1
+#define SGR_ADAM_OVERLAP_WAVES_DEFAULT 512
 int sgr_adam_overlap();   // capi.hip: process-wide switch (sgr_set_adam_overlap)
 int sgr_rows_by_reach();  // capi.hip: process-wide switch (sgr_set_rows_by_reach)
-int sgr_adam_overlap_k(); // capi.hip: SgrShAdamJob.k (SGR_ADAM_OVERLAP_K in the environment)
+int sgr_adam_overlap_waves(); // capi.hip: SgrShAdamJob.n_adam (SGR_ADAM_OVERLAP_WAVES in the environment)
 // sgr_adam_step_ex with the same guard (adam.hip)
 int sgr_adam_launch(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,
                     const long long* seg_begin, const long long* seg_end, const float* seg_lr_a, const float* seg_lr_b,

@@ -249,7 +249,7 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
         SgrShAdamJob job = {};
         if (split) {
             if (ex->step < 1) return tfail(SGR_E_INVALID, "sgr_trainer_step: exchange description missing");
-            job.P = P; job.k = sgr_adam_overlap_k();
+            job.P = P; job.n_adam = sgr_adam_overlap_waves();
             job.sh = flat + c.off_features; job.exp_avg = c.exp_avg + c.off_features; job.exp_avg_sq = c.exp_avg_sq + c.off_features;
             job.reach = reach;
             job.lr_dc = c.lr_features_dc; job.lr_rest = c.lr_features_rest; job.b1 = c.beta1; job.b2 = c.beta2;
