@@ -2,7 +2,7 @@
 yardsticks per operation (the convention of oracle/loss_reference.py):
 
     Adam                    sugar_amd/csrc/adam.hip          k_adam, k_adam_multi                 torch.optim.Adam, gaussian_model.py:152-166
-    SH gradient over views  sugar_amd/csrc/preprocess.hip    k_sh_grad_from_views, k_sh_adam_*    backward.cu:47-97 per view, summed
+    SH gradient over views  sugar_amd/csrc/sh_adam.hip       k_sh_grad_from_views, k_sh_adam_*    backward.cu:47-97 per view, summed
     activations             sugar_amd/csrc/activations.hip   k_activations_fwd / _bwd             gaussian_model.py:92-117
 
 Inputs are the float32 arrays a kernel gets; every restatement computes in float64 from them.  A condition magnitude is the restated
@@ -178,7 +178,7 @@ def sh_grad_from_views(means, campos, dcolor, D, M, dtype=torch.float64):
 
 
 def sh_grad_from_views_f32(means, campos, dcolor, D, M):
-    """yardstick (a): preprocess.hip::sh_grad_sum_over_views in numpy float32, operation by operation in its written order -> [P, M, 3]"""
+    """yardstick (a): sh_adam.hip::sh_grad_sum_over_views in numpy float32, operation by operation in its written order -> [P, M, 3]"""
     f = np.float32
     means, campos, dcolor = (np.asarray(a, f) for a in (means, campos, dcolor))
     C1, C2, C3 = f(SH_C1), [f(c) for c in SH_C2], [f(c) for c in SH_C3]

@@ -22,6 +22,8 @@ ARCH = "gfx950"
 # (individually rounded IEEE ops, see csrc/preprocess.hip); the blend kernels may contract to FMA.
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off"],
+    "sh_adam.hip": ["-ffp-contract=off"],  # the SH gradient restates the backward preprocess; dense, masked and zero-gradient updates leave the same bits
+    "sh_rgb.hip": ["-ffp-contract=off"],   # get_points_rgb on the rasterizer's individually rounded SH evaluation (csrc/sgr_sh.h)
     "binning.hip": ["-ffp-contract=off"],
     "binning2.hip": ["-ffp-contract=off"],
     "blend.hip": ["-fno-slp-vectorize"],  # the auto-formed v_pk_* pairs cost more v_mov shuffles than they save

@@ -1,4 +1,5 @@
-// capi.hip -- host orchestration and the C ABI of include/sugar_raster.h.
+// capi.hip -- host orchestration and the C ABI of the rasterizer (include/sugar_raster.h: forward, backward, mark_visible, the scratch
+// layouts, the stage profile and the error message; every other kernel family keeps its entry points in its own unit).
 //
 // Mirrors the call structure of CudaRasterizer::Rasterizer::{forward,backward,markVisible}
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:141-153, 198-336, 340-434) on a caller-supplied HIP stream.
@@ -137,37 +138,10 @@ uint32_t sgr_deep_min()
     return (uint32_t)g_deep_min;
 }
 
-// SH-Adam of unreached Gaussians inside the blend backward's launch (include/sugar_raster.h: sgr_set_adam_overlap); SGR_ADAM_OVERLAP
-// in the environment sets the default, SGR_ADAM_OVERLAP_WAVES the persistent Adam workgroups in front of the blend's (a multiple of 8)
-static int g_adam_overlap = -1;
-int sgr_adam_overlap()
-{
-    if (g_adam_overlap < 0) { const char* e = getenv("SGR_ADAM_OVERLAP"); g_adam_overlap = e ? (e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0)) : SGR_ADAM_OVERLAP_DEFAULT; }
-    return g_adam_overlap;
-}
-int sgr_adam_overlap_waves()
-{
-    const char* e = getenv("SGR_ADAM_OVERLAP_WAVES");  // (read per step: one getenv, and a test or an A/B run can change it in-process)
-    const int n = e ? atoi(e) : SGR_ADAM_OVERLAP_WAVES_DEFAULT;
-    return (n < 8 || (n & 7) || n > 65536) ? SGR_ADAM_OVERLAP_WAVES_DEFAULT : n;
-}
-// Backward preprocess of the train step by reach flag (include/sugar_raster.h: sgr_set_rows_by_reach); SGR_ROWS_BY_REACH=0 / 1 in the
-// environment sets the default (on)
-static int g_rows_by_reach = -1;
-int sgr_rows_by_reach()
-{
-    if (g_rows_by_reach < 0) { const char* e = getenv("SGR_ROWS_BY_REACH"); g_rows_by_reach = (e && e[0] == '0') ? 0 : 1; }
-    return g_rows_by_reach;
-}
-
 extern "C" {
 
 int sgr_abi_version(void) { return SGR_ABI_VERSION; }
-void sgr_set_rows_by_reach(int on) { g_rows_by_reach = on ? 1 : 0; }
-int sgr_get_rows_by_reach(void) { return sgr_rows_by_reach(); }
 size_t sgr_geom_rowdirty_offset_bytes(int P) { return sgr_geom_rowdirty_offset(P); }
-void sgr_set_adam_overlap(int on) { g_adam_overlap = on == 2 ? 2 : (on ? 1 : 0); }
-int sgr_get_adam_overlap(void) { return sgr_adam_overlap(); }
 size_t sgr_geom_reach_offset_bytes(int P) { return sgr_geom_reach_offset(P); }
 void sgr_set_deep_min(int entries) { g_deep_min = entries > 0 ? entries : 0; }
 int sgr_get_deep_min(void) { return (int)sgr_deep_min(); }
@@ -697,117 +671,6 @@ size_t sgr_bin2_bytes(int P, int width, int height)
 {
     const ImgLayout IL = sgr_img_layout(width, height);
     return sgr_bin2_layout(P, IL.gx, IL.gy).total;
-}
-
-int sgr_sh_grad_from_views(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
-                           const float* dcolor_all, int64_t view_stride, float* dL_dsh, void* stream)
-{
-    if (P <= 0) return 0;
-    if (n_views <= 0 || D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16 || !means3D || !campos_all || !dcolor_all || !dL_dsh)
-        return fail(SGR_E_INVALID, "sgr_sh_grad_from_views: bad arguments");
-    if (view_stride != 0 && view_stride < P) return fail(SGR_E_INVALID, "sgr_sh_grad_from_views: view_stride < P");
-    sgr_launch_sh_grad_from_views(P, n_views, D, M, (size_t)(view_stride ? view_stride : P), means3D, campos_all, dcolor_all, dL_dsh,
-                                  (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_grad_from_views: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int sgr_sh_adam_from_views_ex(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
-                              const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq, float lr_dc,
-                              float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, float* dmean_extra,
-                              void* stream)
-{
-    if (P <= 0) return 0;
-    if (n_views <= 0 || D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16 || step < 1 || !means3D || !campos_all || !dcolor_all ||
-        !sh_params || !exp_avg || !exp_avg_sq)
-        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views: bad argument");
-    float bc1, bc2_sqrt;
-    sgr_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
-    if (view_stride != 0 && view_stride < P) return fail(SGR_E_INVALID, "sgr_sh_adam_from_views: view_stride < P");
-    if (dmean_extra && (M != 16 || ((uintptr_t)sh_params & 15)))
-        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_ex: dmean_extra needs M == 16 and 16-byte aligned sh_params");
-    sgr_launch_sh_adam_from_views(P, n_views, D, M, (size_t)(view_stride ? view_stride : P), means3D, campos_all, dcolor_all, sh_params, exp_avg, exp_avg_sq, lr_dc, lr_rest,
-                                  beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, dmean_extra, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_from_views: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// the two halves of SH-Adam split by reach flag (csrc/sh_adam_update.h)
-static bool sh_split_ok(int M, const float* sh, const float* m, const float* v)
-{
-    return M == 16 && ((((uintptr_t)sh | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-}
-
-// (n_adam == 0: one wave per 64 Gaussians; otherwise that many persistent waves)
-static int sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
-                             float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
-                             uint32_t guard_capacity, int n_adam, void* stream)
-{
-    if (P <= 0) return 0;
-    if (step < 1 || !sh_params || !exp_avg || !exp_avg_sq || !reach) return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad: bad argument");
-    if (!sh_split_ok(M, sh_params, exp_avg, exp_avg_sq))
-        return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad: needs M == 16 and 16-byte aligned buffers");
-    SgrShAdamJob job = {};
-    job.P = P; job.sh = sh_params; job.exp_avg = exp_avg; job.exp_avg_sq = exp_avg_sq; job.reach = reach;
-    job.lr_dc = lr_dc; job.lr_rest = lr_rest; job.b1 = beta1; job.b2 = beta2; job.omb1 = sgr_one_minus(beta1); job.omb2 = sgr_one_minus(beta2);
-    job.eps = eps; job.grad_scale = grad_scale; job.zero = 0.f; job.guard = guard_header; job.guard_cap = guard_capacity;
-    sgr_bias_corrections(beta1, beta2, step, &job.bc1, &job.bc2_sqrt);
-    job.n_adam = n_adam;
-    if (n_adam > 0) sgr_launch_sh_adam_zero_persistent(job, (hipStream_t)stream);
-    else sgr_launch_sh_adam_zero(job, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_zero_grad: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int sgr_sh_adam_zero_grad(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
-                          float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, const uint32_t* guard_header,
-                          uint32_t guard_capacity, void* stream)
-{
-    return sh_adam_zero_grad(P, M, sh_params, exp_avg, exp_avg_sq, reach, lr_dc, lr_rest, beta1, beta2, eps, step, grad_scale, guard_header,
-                             guard_capacity, 0, stream);
-}
-
-int sgr_sh_adam_zero_grad_persistent(int P, int M, float* sh_params, float* exp_avg, float* exp_avg_sq, const uint8_t* reach, float lr_dc,
-                                     float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
-                                     const uint32_t* guard_header, uint32_t guard_capacity, int n_adam, void* stream)
-{
-    if (n_adam < 8 || (n_adam & 7) || n_adam > 65536)
-        return fail(SGR_E_INVALID, "sgr_sh_adam_zero_grad_persistent: n_adam must be a multiple of 8 in [8, 65536]");
-    return sh_adam_zero_grad(P, M, sh_params, exp_avg, exp_avg_sq, reach, lr_dc, lr_rest, beta1, beta2, eps, step, grad_scale, guard_header,
-                             guard_capacity, n_adam, stream);
-}
-
-int sgr_sh_adam_from_views_masked(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
-                                  const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq,
-                                  float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
-                                  uint8_t* reach, const uint32_t* guard_header, uint32_t guard_capacity, void* stream)
-{
-    if (P <= 0) return 0;
-    if (n_views <= 0 || D < 0 || D > 3 || M < (D + 1) * (D + 1) || step < 1 || !means3D || !campos_all || !dcolor_all || !sh_params ||
-        !exp_avg || !exp_avg_sq || !reach)
-        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: bad argument");
-    if (view_stride != 0 && view_stride < P) return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: view_stride < P");
-    if (!sh_split_ok(M, sh_params, exp_avg, exp_avg_sq))
-        return fail(SGR_E_INVALID, "sgr_sh_adam_from_views_masked: needs M == 16 and 16-byte aligned buffers");
-    float bc1, bc2_sqrt;
-    sgr_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
-    sgr_launch_sh_adam_from_views(P, n_views, D, M, (size_t)(view_stride ? view_stride : P), means3D, campos_all, dcolor_all, sh_params, exp_avg,
-                                  exp_avg_sq, lr_dc, lr_rest, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, nullptr, (hipStream_t)stream,
-                                  guard_header, guard_capacity, reach);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SGR_E_HIP, std::string("sh_adam_from_views_masked: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int sgr_sh_adam_from_views(int P, int n_views, int D, int M, const float* means3D, const float* campos_all,
-                           const float* dcolor_all, int64_t view_stride, float* sh_params, float* exp_avg, float* exp_avg_sq, float lr_dc,
-                           float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale, void* stream)
-{
-    return sgr_sh_adam_from_views_ex(P, n_views, D, M, means3D, campos_all, dcolor_all, view_stride, sh_params, exp_avg, exp_avg_sq, lr_dc,
-                                     lr_rest, beta1, beta2, eps, step, grad_scale, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// preprocess.hip -- per-Gaussian kernels for gfx950: frustum test, forward preprocess (projection, EWA
-// covariance, tile rectangle, SH colour, depth-sort key) and the fused backward preprocess.
+// preprocess.hip -- the rasterizer's per-Gaussian kernels for gfx950: frustum test, forward preprocess (projection, EWA
+// covariance, tile rectangle, SH colour, depth-sort key), the depth keys on their own, the fused backward preprocess (dense, and
+// packed by reach flag) and the clamp-masked colour gradients.  The SH evaluation they share with the SH optimiser (sh_adam.hip)
+// and with get_points_rgb (sh_rgb.hip) is sgr_sh.h.
 //
 // Replaces (does not translate) the reference kernels
 //   checkFrustum        DGR/cuda_rasterizer/rasterizer_impl.cu:54-66
@@ -18,20 +20,9 @@
 // instead of being stored (24 B/Gaussian of HBM traffic each way for ~40 flops).
 #include "../../include/sugar_raster.h"
 #include "sgr_common.h"
-#include "sh_adam_update.h"
+#include "sgr_sh.h"
 
 namespace {
-
-__device__ __constant__ const float SH_C0 = 0.28209479177387814f;
-__device__ __constant__ const float SH_C1 = 0.4886025119029199f;
-__device__ __constant__ const float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                                 -1.0925484305920792f, 0.5462742152960396f};
-__device__ __constant__ const float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                                 0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                                 -0.5900435899266435f};
-
-__device__ __forceinline__ float fmin_(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float fmax_(float a, float b) { return a > b ? a : b; }
 
 // float -> int with saturation and NaN -> 0 (what v_cvt_i32_f32 does; spelled out so it cannot be UB)
 __device__ __forceinline__ int f2i_sat(float v)
@@ -119,147 +110,6 @@ __device__ __forceinline__ void cov2d_from_T(const float T[2][3], const float* c
     a = A[0][0] * T[0][0] + A[1][0] * T[0][1] + A[2][0] * T[0][2];
     b = A[0][1] * T[0][0] + A[1][1] * T[0][1] + A[2][1] * T[0][2];
     c = A[0][1] * T[1][0] + A[1][1] * T[1][1] + A[2][1] * T[1][2];
-}
-
-// SH -> RGB for channel c; sh points at this Gaussian's [M][3] coefficient block
-__device__ __forceinline__ float sh_channel(int deg, const float* sh, int c, float x, float y, float z)
-{
-#define SH(k) sh[3 * (k) + c]
-    float r = SH_C0 * SH(0);
-    if (deg > 0) {
-        r = r - SH_C1 * y * SH(1) + SH_C1 * z * SH(2) - SH_C1 * x * SH(3);
-        if (deg > 1) {
-            float xx = x * x, yy = y * y, zz = z * z;
-            float xy = x * y, yz = y * z, xz = x * z;
-            r = r + SH_C2[0] * xy * SH(4) + SH_C2[1] * yz * SH(5) + SH_C2[2] * (2.0f * zz - xx - yy) * SH(6) +
-                SH_C2[3] * xz * SH(7) + SH_C2[4] * (xx - yy) * SH(8);
-            if (deg > 2) {
-                r = r + SH_C3[0] * y * (3.0f * xx - yy) * SH(9) + SH_C3[1] * xy * z * SH(10) +
-                    SH_C3[2] * y * (4.0f * zz - xx - yy) * SH(11) +
-                    SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * SH(12) +
-                    SH_C3[4] * x * (4.0f * zz - xx - yy) * SH(13) + SH_C3[5] * z * (xx - yy) * SH(14) +
-                    SH_C3[6] * x * (xx - 3.0f * yy) * SH(15);
-            }
-        }
-    }
-#undef SH
-    return r + 0.5f;
-}
-
-// Load this Gaussian's SH block into registers.  The [P,M,3] layout gives each lane 12*M contiguous
-// bytes; with M == 16 and a 16-B aligned base (FAST: decided by the launcher, so the kernel holds ONE load path and the
-// loaded values need not meet another path's at a join, which would make the compiler wait for them on the spot) that is
-// twelve dwordx4 loads per lane.
-template <int MAXC, bool FAST = false>
-__device__ __forceinline__ void load_sh(const float* shs, size_t idx, int M, float* sh)
-{
-    const float* src = shs + idx * (size_t)M * 3;
-    const int n = M * 3;
-    if (FAST) {
-        const float4* s4 = reinterpret_cast<const float4*>(shs) + idx * 12;
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            float4 v = s4[i];
-            sh[4 * i] = v.x; sh[4 * i + 1] = v.y; sh[4 * i + 2] = v.z; sh[4 * i + 3] = v.w;
-        }
-    } else if (MAXC == 48 && n == 48 && ((uintptr_t)src & 15) == 0) {
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            float4 v = s4[i];
-            sh[4 * i] = v.x; sh[4 * i + 1] = v.y; sh[4 * i + 2] = v.z; sh[4 * i + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < MAXC; i++) sh[i] = (i < n) ? src[i] : 0.0f;
-    }
-}
-__host__ __device__ __forceinline__ bool sh_fast_layout(const float* shs, int M) { return shs && M == 16 && ((uintptr_t)shs & 15) == 0; }
-
-// d RGB_c / d(view direction) for one colour channel from its 16 coefficients h[k] (backward.cu:99-131): the derivative half
-// of computeColorFromSH's backward, shared by the backward preprocess kernel and the SH-Adam kernel.
-__device__ __forceinline__ void sh_dir_channel(const int deg, const float* h, const float x, const float y, const float z,
-                                               float& dRGBdx, float& dRGBdy, float& dRGBdz)
-{
-    dRGBdx = 0; dRGBdy = 0; dRGBdz = 0;
-    if (deg > 0) {
-        dRGBdx = -SH_C1 * h[3]; dRGBdy = -SH_C1 * h[1]; dRGBdz = SH_C1 * h[2];
-        if (deg > 1) {
-            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            dRGBdx += SH_C2[0] * y * h[4] + SH_C2[2] * 2.f * -x * h[6] + SH_C2[3] * z * h[7] + SH_C2[4] * 2.f * x * h[8];
-            dRGBdy += SH_C2[0] * x * h[4] + SH_C2[1] * z * h[5] + SH_C2[2] * 2.f * -y * h[6] + SH_C2[4] * 2.f * -y * h[8];
-            dRGBdz += SH_C2[1] * y * h[5] + SH_C2[2] * 2.f * 2.f * z * h[6] + SH_C2[3] * x * h[7];
-            if (deg > 2) {
-                dRGBdx += (SH_C3[0] * h[9] * 3.f * 2.f * xy + SH_C3[1] * h[10] * yz + SH_C3[2] * h[11] * -2.f * xy +
-                           SH_C3[3] * h[12] * -3.f * 2.f * xz + SH_C3[4] * h[13] * (-3.f * xx + 4.f * zz - yy) +
-                           SH_C3[5] * h[14] * 2.f * xz + SH_C3[6] * h[15] * 3.f * (xx - yy));
-                dRGBdy += (SH_C3[0] * h[9] * 3.f * (xx - yy) + SH_C3[1] * h[10] * xz +
-                           SH_C3[2] * h[11] * (-3.f * yy + 4.f * zz - xx) + SH_C3[3] * h[12] * -3.f * 2.f * yz +
-                           SH_C3[4] * h[13] * -2.f * xy + SH_C3[5] * h[14] * -2.f * yz + SH_C3[6] * h[15] * -3.f * 2.f * xy);
-                dRGBdz += (SH_C3[1] * h[10] * xy + SH_C3[2] * h[11] * 4.f * 2.f * yz +
-                           SH_C3[3] * h[12] * 3.f * (2.f * zz - xx - yy) + SH_C3[4] * h[13] * 4.f * 2.f * xz +
-                           SH_C3[5] * h[14] * (xx - yy));
-            }
-        }
-    }
-}
-
-// The 16 SH basis values of computeColorFromSH's backward (backward.cu:47-97: dRGBdsh0 ... dRGBdsh15), zero beyond the active
-// degree; the very expressions sh_backward multiplies by dL/dRGB, so basis[k] * dL_dRGB[c] is bit-identical to its DSH(k).
-__device__ __forceinline__ void sh_basis16(const int deg, const float x, const float y, const float z, float* b)
-{
-#pragma unroll
-    for (int k = 0; k < 16; k++) b[k] = 0.0f;
-    b[0] = SH_C0;
-    if (deg > 0) {
-        b[1] = -SH_C1 * y; b[2] = SH_C1 * z; b[3] = -SH_C1 * x;
-        if (deg > 1) {
-            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            b[4] = SH_C2[0] * xy; b[5] = SH_C2[1] * yz; b[6] = SH_C2[2] * (2.f * zz - xx - yy); b[7] = SH_C2[3] * xz;
-            b[8] = SH_C2[4] * (xx - yy);
-            if (deg > 2) {
-                b[9] = SH_C3[0] * y * (3.f * xx - yy); b[10] = SH_C3[1] * xy * z; b[11] = SH_C3[2] * y * (4.f * zz - xx - yy);
-                b[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy); b[13] = SH_C3[4] * x * (4.f * zz - xx - yy);
-                b[14] = SH_C3[5] * z * (xx - yy); b[15] = SH_C3[6] * x * (xx - 3.f * yy);
-            }
-        }
-    }
-}
-
-// computeColorFromSH backward for one Gaussian (backward.cu:47-137): dsh[k][c] = basis_k(dir) * masked dL/dRGB[c] and the
-// gradient w.r.t. the (normalised) view direction.  `clamped` bit c set = channel c was clamped to 0 by the forward.
-__device__ __forceinline__ void sh_backward(const int deg, const float* sh, const float* dcol, const uint32_t clamped,
-                                            const float x, const float y, const float z, float* dsh, float* dL_ddir)
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-#define DSH(k) dsh[3 * (k) + c]
-        float dL_dRGB = dcol[c] * (((clamped >> c) & 1u) ? 0.0f : 1.0f);
-        DSH(0) = SH_C0 * dL_dRGB;
-        if (deg > 0) {
-            DSH(1) = (-SH_C1 * y) * dL_dRGB; DSH(2) = (SH_C1 * z) * dL_dRGB; DSH(3) = (-SH_C1 * x) * dL_dRGB;
-            if (deg > 1) {
-                float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                DSH(4) = (SH_C2[0] * xy) * dL_dRGB; DSH(5) = (SH_C2[1] * yz) * dL_dRGB;
-                DSH(6) = (SH_C2[2] * (2.f * zz - xx - yy)) * dL_dRGB; DSH(7) = (SH_C2[3] * xz) * dL_dRGB;
-                DSH(8) = (SH_C2[4] * (xx - yy)) * dL_dRGB;
-                if (deg > 2) {
-                    DSH(9) = (SH_C3[0] * y * (3.f * xx - yy)) * dL_dRGB; DSH(10) = (SH_C3[1] * xy * z) * dL_dRGB;
-                    DSH(11) = (SH_C3[2] * y * (4.f * zz - xx - yy)) * dL_dRGB;
-                    DSH(12) = (SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * dL_dRGB;
-                    DSH(13) = (SH_C3[4] * x * (4.f * zz - xx - yy)) * dL_dRGB;
-                    DSH(14) = (SH_C3[5] * z * (xx - yy)) * dL_dRGB; DSH(15) = (SH_C3[6] * x * (xx - 3.f * yy)) * dL_dRGB;
-                }
-            }
-        }
-#undef DSH
-        float h[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) h[k] = sh[3 * k + c];
-        float dRGBdx, dRGBdy, dRGBdz;
-        sh_dir_channel(deg, h, x, y, z, dRGBdx, dRGBdy, dRGBdz);
-        dL_ddir[0] += dRGBdx * dL_dRGB; dL_ddir[1] += dRGBdy * dL_dRGB; dL_ddir[2] += dRGBdz * dL_dRGB;
-    }
 }
 
 __global__ void __launch_bounds__(256) k_mark_visible(int P, const float* __restrict__ means3D,
@@ -986,9 +836,6 @@ __global__ void __launch_bounds__(256, SGR_PRE_BWD_BLOCKS) k_preprocess_bwd_pack
     preprocess_bwd_lane<false, SH>(a, nullptr, idx0, in_order);
 }
 
-// dL/dsh[k][c] = sum over views v of  basis_k(dir_v) * g_v[c]   with dir_v = normalize(mean - campos_v) and g_v the
-// clamp-masked dL/dRGB of view v -- exactly the per-view SH backward (backward.cu:47-97) summed over views, but the views
-// exchange 3 floats per Gaussian instead of 3*M.  dirs use the same arithmetic as the forward (glm::length, division).
 // The clamp-masked colour gradients of the compact mode on their own: they only need the blend backward's sums, so a
 // trainer can start exchanging them while the backward preprocess is still running (sgr_backward_phase).
 __global__ void __launch_bounds__(256) k_masked_colors(int P, const GeomRec* __restrict__ rec, const float* __restrict__ acc,
@@ -1006,385 +853,6 @@ __global__ void __launch_bounds__(256) k_masked_colors(int P, const GeomRec* __r
     out[i3] = (clamped & 1u) ? 0.f : s0.x;
     out[i3 + 1] = (clamped & 2u) ? 0.f : s0.y;
     out[i3 + 2] = (clamped & 4u) ? 0.f : s0.z;
-}
-
-// dL/dmean3D through the view direction, summed over the views (the tail of the backward preprocess kernel,
-// backward.cu:99-139 + dnormvdv, moved next to the only other reader of the SH coefficients; `row` = this Gaussian's 48
-// coefficients in LDS).  Same arithmetic, operation for operation, as k_preprocess_bwd (sh_backward).  One colour channel at
-// a time, its 16 coefficients fetched from the LDS row: with all 48 in registers next to the expanded polynomial the kernel
-// needed 190 VGPRs, two waves per SIMD, and lost in bandwidth what the backward preprocess kernel saved.
-__device__ __forceinline__ void sh_dir_sum_over_views(int idx, size_t P, int V, int D, const float* __restrict__ means3D,
-                                                      const float* __restrict__ campos, const float* __restrict__ dcolor,
-                                                      const float* row, float* dm)
-{
-    const size_t i3 = 3 * (size_t)idx;
-    const float mx = means3D[i3], my = means3D[i3 + 1], mz = means3D[i3 + 2];
-    dm[0] = 0.f; dm[1] = 0.f; dm[2] = 0.f;
-    for (int v = 0; v < V; v++) {
-        const float* g = dcolor + ((size_t)v * P + idx) * 3;
-        const float g0 = g[0], g1 = g[1], g2 = g[2];
-        if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;  // culled or fully clamped in this view
-        const float dx = mx - campos[3 * v], dy = my - campos[3 * v + 1], dz = mz - campos[3 * v + 2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float x = dx / len, y = dy / len, z = dz / len;
-        float dL_ddir[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int c = 0; c < 3; c++) {
-            float h[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) h[k] = row[3 * k + c];
-            const float dL_dRGB = (c == 0 ? g0 : (c == 1 ? g1 : g2)) * 1.0f;  // (sh_backward's mask factor: the colours arrive masked)
-            float dRGBdx, dRGBdy, dRGBdz;
-            sh_dir_channel(D, h, x, y, z, dRGBdx, dRGBdy, dRGBdz);
-            dL_ddir[0] += dRGBdx * dL_dRGB; dL_ddir[1] += dRGBdy * dL_dRGB; dL_ddir[2] += dRGBdz * dL_dRGB;
-        }
-        // dnormvdv, auxiliary.h:107-117
-        const float sum2 = dx * dx + dy * dy + dz * dz;
-        const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-        dm[0] += ((+sum2 - dx * dx) * dL_ddir[0] - dy * dx * dL_ddir[1] - dz * dx * dL_ddir[2]) * invsum32;
-        dm[1] += (-dx * dy * dL_ddir[0] + (sum2 - dy * dy) * dL_ddir[1] - dz * dy * dL_ddir[2]) * invsum32;
-        dm[2] += (-dx * dz * dL_ddir[0] - dy * dz * dL_ddir[1] + (sum2 - dz * dz) * dL_ddir[2]) * invsum32;
-    }
-}
-
-__device__ __forceinline__ void sh_grad_sum_over_views(int idx, size_t P, int V, int D, const float* __restrict__ means3D,
-                                                       const float* __restrict__ campos, const float* __restrict__ dcolor,
-                                                       float* acc)
-{
-    const size_t i3 = 3 * (size_t)idx;
-    const float mx = means3D[i3], my = means3D[i3 + 1], mz = means3D[i3 + 2];
-#pragma unroll
-    for (int k = 0; k < 48; k++) acc[k] = 0.f;
-    for (int v = 0; v < V; v++) {
-        const float* g = dcolor + ((size_t)v * P + idx) * 3;
-        const float g0 = g[0], g1 = g[1], g2 = g[2];
-        if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;  // culled or fully clamped in this view
-        float dx = mx - campos[3 * v], dy = my - campos[3 * v + 1], dz = mz - campos[3 * v + 2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float x = dx / len, y = dy / len, z = dz / len;
-        float b[16];
-        b[0] = SH_C0;
-        if (D > 0) {
-            b[1] = -SH_C1 * y; b[2] = SH_C1 * z; b[3] = -SH_C1 * x;
-            if (D > 1) {
-                const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                b[4] = SH_C2[0] * xy; b[5] = SH_C2[1] * yz; b[6] = SH_C2[2] * (2.f * zz - xx - yy);
-                b[7] = SH_C2[3] * xz; b[8] = SH_C2[4] * (xx - yy);
-                if (D > 2) {
-                    b[9] = SH_C3[0] * y * (3.f * xx - yy); b[10] = SH_C3[1] * xy * z;
-                    b[11] = SH_C3[2] * y * (4.f * zz - xx - yy); b[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy);
-                    b[13] = SH_C3[4] * x * (4.f * zz - xx - yy); b[14] = SH_C3[5] * z * (xx - yy);
-                    b[15] = SH_C3[6] * x * (xx - 3.f * yy);
-                }
-            }
-        }
-        const int nb = (D + 1) * (D + 1);
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            if (k < nb) { acc[3 * k] += b[k] * g0; acc[3 * k + 1] += b[k] * g1; acc[3 * k + 2] += b[k] * g2; }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) k_sh_grad_from_views(int P, int V, int D, int M, size_t vstride,
-                                                            const float* __restrict__ means3D,
-                                                            const float* __restrict__ campos, const float* __restrict__ dcolor,
-                                                            float* __restrict__ dL_dsh)
-{
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= P) return;
-    float acc[48];
-    sh_grad_sum_over_views(idx, vstride, V, D, means3D, campos, dcolor, acc);
-    const int n_sh = 3 * M;
-    float* dst = dL_dsh + (size_t)idx * n_sh;
-    if (n_sh == 48 && ((uintptr_t)dst & 15) == 0) {
-        float4* d4 = reinterpret_cast<float4*>(dst);
-#pragma unroll
-        for (int i = 0; i < 12; i++) { float4 o = {acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]}; d4[i] = o; }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 48; i++) if (i < n_sh) dst[i] = acc[i];
-    }
-}
-
-// The same sum, consumed on the spot: Adam on the Gaussian's SH coefficients (adam.hip's update, lr_dc for the three DC
-// values and lr_rest for the others: gaussian_model.py:157-158) without ever writing the 48-float gradient to memory.
-struct ShAdamArgs {
-    float lr_dc, lr_rest, b1, b2, omb1, omb2, eps, bc1, bc2_sqrt, grad_scale;
-    const uint32_t* guard; uint32_t guard_cap;  // forward header + list capacity: the step is a no-op if that forward was invalid (NULL: no check)
-    uint8_t* reach;  // MASKED: the reach flags (sh_adam_update.h)
-};
-
-// One wave per 64 Gaussians.  Phase 1: lane = Gaussian, the 48 sums in registers, dropped into an LDS panel (row stride 52
-// floats: conflict-free for 16-byte accesses).  Phase 2: the wave walks the 64 x 48 floats of parameters and moments as
-// one contiguous stream, one float4 per lane and step (a lane-per-Gaussian walk touches 64 cache lines per instruction
-// and ran at 2 TB/s).
-#define SHA_STRIDE 52
-// DIR (dmean_extra != NULL, M == 16): phase 1 also loads the Gaussian's 48 coefficients (the wave's 12 KB block, which
-// phase 2 then streams out of the cache) and writes the view-direction part of dL/dmean3D, summed over the views, to
-// dmean_extra[P][3]; the flat Adam kernel adds it to the position gradient (sgr_adam_step_ex).
-// MASKED (M == 16, aligned buffers, no DIR): only the rows whose reach flag is set are updated -- the others got their zero-gradient
-// step from sgr_sh_adam_zero_wave --, and the wave puts its 64 flags back to 0 (it is their last reader, as k_preprocess_bwd is the
-// accumulator table's).  Unflagged rows run no phase 1 and load no colour, and phase 2 walks the flagged rows only: their lane
-// numbers are compacted into an LDS list, and the stream is n_flagged x 12 float4 instead of 64 x 12 (a fifth of the steps on the
-// metric scene; clamped addresses as below, not lane-predicated loads).
-template <bool DIR, bool MASKED = false>
-__global__ void __launch_bounds__(64) k_sh_adam_from_views(int P, int V, int D, int M, size_t vstride,
-                                                           const float* __restrict__ means3D,
-                                                           const float* __restrict__ campos, const float* __restrict__ dcolor,
-                                                           float* __restrict__ sh, float* __restrict__ exp_avg,
-                                                           float* __restrict__ exp_avg_sq, ShAdamArgs a,
-                                                           float* __restrict__ dmean_extra)
-{
-    __shared__ __attribute__((aligned(16))) float s_g[64 * SHA_STRIDE];
-    if (a.guard && SGR_FORWARD_INVALID(a.guard, a.guard_cap)) return;
-    const int lane = threadIdx.x;
-    const int g0 = blockIdx.x * 64;
-    const int idx = g0 + lane;
-    unsigned long long flagged = ~0ull;  // MASKED: bit g <=> row g0 + g is updated here
-    if (MASKED) {
-        flagged = __ballot(idx < P && a.reach[min(idx, P - 1)] != 0);
-        if (flagged == 0ull) return;
-    }
-    float4 pkeep[12];  // DIR: the wave's 64 x 48 coefficients in the streaming layout of phase 2 (read from memory once)
-    if (DIR) {
-        // coalesced into the panel (row = Gaussian) for the direction term, and kept in registers for the Adam update
-        // (12 loads at a 192-byte lane stride straight from memory cost this streaming kernel 25 us; re-reading the block in
-        // phase 2 gives back what the backward preprocess kernel saved)
-        const float4* p4 = reinterpret_cast<const float4*>(sh + (size_t)g0 * 48);
-        const int n4 = min(64, P - g0) * 12;
-#pragma unroll
-        for (int st = 0; st < 12; st++) pkeep[st] = p4[min(st * 64 + lane, n4 - 1)];
-#pragma unroll
-        for (int st = 0; st < 12; st++) {
-            const int e4 = st * 64 + lane;
-            if (e4 < n4) { const int g = e4 / 12; *reinterpret_cast<float4*>(s_g + g * SHA_STRIDE + 4 * (e4 - g * 12)) = pkeep[st]; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (DIR && idx < P) {
-        float dm[3];
-        sh_dir_sum_over_views(idx, vstride, V, D, means3D, campos, dcolor, s_g + lane * SHA_STRIDE, dm);
-        dmean_extra[3 * (size_t)idx] = dm[0]; dmean_extra[3 * (size_t)idx + 1] = dm[1]; dmean_extra[3 * (size_t)idx + 2] = dm[2];
-    }
-    if (DIR) {  // every lane is done with its coefficients before any lane overwrites a row with gradient sums
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    {
-        float acc[48];
-        if (idx < P && ((flagged >> lane) & 1ull)) {
-            sh_grad_sum_over_views(idx, vstride, V, D, means3D, campos, dcolor, acc);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 48; k++) acc[k] = 0.f;
-        }
-        float4* row = reinterpret_cast<float4*>(s_g + lane * SHA_STRIDE);
-#pragma unroll
-        for (int i = 0; i < 12; i++) row[i] = make_float4(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int n_sh = 3 * M;
-    const int live = min(64, P - g0);
-    auto upd = [&](int c, float g, float& p, float& m, float& v) {
-        sh_adam_update(g, p, m, v, c < 3 ? a.lr_dc : a.lr_rest, a.grad_scale, a.b1, a.b2, a.omb1, a.omb2, a.eps, a.bc1, a.bc2_sqrt);
-    };
-    const size_t base = (size_t)g0 * n_sh;
-    if (MASKED) {  // (n_sh == 48 and aligned buffers: the launcher's callers have checked)
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        __shared__ int s_row[64];  // the flagged rows of the wave, in order
-        const int n4f = 12 * __popcll(flagged);
-        if ((flagged >> lane) & 1ull)
-            s_row[__builtin_amdgcn_mbcnt_hi((uint32_t)(flagged >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)flagged, 0u))] = lane;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        f4* p4 = reinterpret_cast<f4*>(sh + base);
-        f4* m4 = reinterpret_cast<f4*>(exp_avg + base);
-        f4* v4 = reinterpret_cast<f4*>(exp_avg_sq + base);
-        constexpr int NB = 4;
-#pragma clang loop unroll(disable)
-        for (int st0 = 0; st0 * 64 < n4f; st0 += NB) {
-            f4 pv[NB], mv[NB], vv[NB];
-            int ee[NB];
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const int j = min((st0 + u) * 64 + lane, n4f - 1);  // float4 index inside the compacted stream
-                const int r = j / 12;
-                ee[u] = s_row[r] * 12 + (j - r * 12);                // ... and inside the wave's 64 x 48 block
-                pv[u] = p4[ee[u]];
-                mv[u] = __builtin_nontemporal_load(&m4[ee[u]]); vv[u] = __builtin_nontemporal_load(&v4[ee[u]]);
-            }
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                if ((st0 + u) * 64 + lane < n4f) {
-                    const int e4 = ee[u], g = e4 / 12, c4 = e4 - g * 12;
-                    const float4 gr = *reinterpret_cast<const float4*>(s_g + g * SHA_STRIDE + 4 * c4);
-                    float p[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, m[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
-                    float v[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-                    const float gq[4] = {gr.x, gr.y, gr.z, gr.w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++) upd(4 * c4 + k, gq[k], p[k], m[k], v[k]);
-                    const f4 po = {p[0], p[1], p[2], p[3]}, mo = {m[0], m[1], m[2], m[3]}, vo = {v[0], v[1], v[2], v[3]};
-                    p4[e4] = po;
-                    __builtin_nontemporal_store(mo, &m4[e4]);
-                    __builtin_nontemporal_store(vo, &v4[e4]);
-                }
-            }
-        }
-    } else if (n_sh == 48 && ((((uintptr_t)sh | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0)) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        f4* p4 = reinterpret_cast<f4*>(sh + base);
-        f4* m4 = reinterpret_cast<f4*>(exp_avg + base);
-        f4* v4 = reinterpret_cast<f4*>(exp_avg_sq + base);
-        const int n4 = live * 12;
-        // four steps at a time: their twelve loads go out together (one at a time -- loads under the lane predicate, every
-        // step waiting for its own -- a wave made twelve serial round trips; addresses are clamped instead)
-        constexpr int NB = DIR ? 2 : 4;  // (DIR holds the parameters in registers already: smaller batches keep it at 3 waves per SIMD)
-#pragma unroll
-        for (int st0 = 0; st0 < 12; st0 += NB) {
-            f4 pv[NB], mv[NB], vv[NB];
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const int e4 = min((st0 + u) * 64 + lane, n4 - 1);  // float4 index inside the wave's 64 x 48 block
-                // the moments are touched once per step: stream them past the caches, the parameters are read again by
-                // the next forward and should stay in the last-level cache
-                if (DIR) { const float4 k = pkeep[st0 + u]; pv[u] = (f4){k.x, k.y, k.z, k.w}; }
-                else pv[u] = p4[e4];
-                mv[u] = __builtin_nontemporal_load(&m4[e4]); vv[u] = __builtin_nontemporal_load(&v4[e4]);
-            }
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const int e4 = (st0 + u) * 64 + lane;
-                if (e4 < n4) {
-                    const int g = e4 / 12, c4 = e4 - g * 12;
-                    const float4 gr = *reinterpret_cast<const float4*>(s_g + g * SHA_STRIDE + 4 * c4);
-                    float p[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, m[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
-                    float v[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-                    const float gq[4] = {gr.x, gr.y, gr.z, gr.w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++) upd(4 * c4 + k, gq[k], p[k], m[k], v[k]);
-                    const f4 po = {p[0], p[1], p[2], p[3]}, mo = {m[0], m[1], m[2], m[3]}, vo = {v[0], v[1], v[2], v[3]};
-                    p4[e4] = po;
-                    __builtin_nontemporal_store(mo, &m4[e4]);
-                    __builtin_nontemporal_store(vo, &v4[e4]);
-                }
-            }
-        }
-    } else {
-        const int n = live * n_sh;
-        for (int e = lane; e < n; e += 64) {
-            const int g = e / n_sh, c = e - g * n_sh;
-            float p = sh[base + e], m = exp_avg[base + e], v = exp_avg_sq[base + e];
-            upd(c, s_g[g * SHA_STRIDE + c], p, m, v);
-            sh[base + e] = p; exp_avg[base + e] = m; exp_avg_sq[base + e] = v;
-        }
-    }
-    if (MASKED && idx < P) a.reach[idx] = 0;
-}
-
-// the zero-gradient half as a launch of its own, one wave per 64 Gaussians: for a step with no blend backward to ride in
-__global__ void __launch_bounds__(64) k_sh_adam_zero(SgrShAdamJob job) { sgr_sh_adam_zero_wave<4>(job, (int)blockIdx.x * 64); }
-// ... and the persistent form the blend backward carries, as a launch of its own: job.n_adam waves, each over every n_adam-th block
-__global__ void __launch_bounds__(64) k_sh_adam_zero_persistent(SgrShAdamJob job) { sgr_sh_adam_zero_persistent(job, (int)blockIdx.x, job.n_adam); }
-
-// ---------------------------------------------------------------------------------------------
-// SuGaR.get_points_rgb (sugar_scene/sugar_model.py:839-883): colours = clamp_min(eval_sh(levels-1, sh, dir) + 0.5, 0) with
-// dir = F.normalize(positions - camera_centers) (or given directions).  The reference spends ~30 elementwise launches and
-// their autograd twins on this every training step (it feeds `colors_precomp`); here it is one lane per point, forward
-// and backward, on the same SH basis code as the rasterizer.  sh rows have a stride of `M` coefficients; `n` are used.
-struct ShRgbArgs {
-    int P, D, M, n;            // D = sh_levels - 1, n = (D+1)^2
-    const float* sh;           // [P, M, 3]
-    const float* positions;    // [P, 3] or null (then `directions` is used as is)
-    const float* centers;      // [n_centers, 3], n_centers in {1, P}
-    int n_centers;
-    const float* directions;   // [P, 3] or null
-};
-
-__device__ __forceinline__ void sh_rgb_dir(const ShRgbArgs& a, int idx, float& x, float& y, float& z, float& vx, float& vy,
-                                           float& vz, float& len)
-{
-    const size_t i3 = 3 * (size_t)idx;
-    if (a.positions) {
-        const size_t c3 = a.n_centers == 1 ? 0 : i3;
-        vx = a.positions[i3] - a.centers[c3]; vy = a.positions[i3 + 1] - a.centers[c3 + 1]; vz = a.positions[i3 + 2] - a.centers[c3 + 2];
-        len = fmax_(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);  // F.normalize: v / max(|v|, eps)
-        x = vx / len; y = vy / len; z = vz / len;
-    } else {
-        x = a.directions[i3]; y = a.directions[i3 + 1]; z = a.directions[i3 + 2];
-        vx = x; vy = y; vz = z; len = 1.f;
-    }
-}
-
-__device__ __forceinline__ void load_sh_n(const float* shs, size_t idx, int M, int n, float* sh)
-{
-    if (n == M) { load_sh<48>(shs, idx, M, sh); return; }
-    const float* src = shs + idx * (size_t)M * 3;
-#pragma unroll
-    for (int i = 0; i < 48; i++) sh[i] = (i < 3 * n) ? src[i] : 0.0f;
-}
-
-__global__ void __launch_bounds__(256) k_sh_to_rgb_fwd(ShRgbArgs a, float* __restrict__ colors)
-{
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= a.P) return;
-    float x, y, z, vx, vy, vz, len;
-    sh_rgb_dir(a, idx, x, y, z, vx, vy, vz, len);
-    float sh[48];
-    load_sh_n(a.sh, idx, a.M, a.n, sh);
-    const size_t i3 = 3 * (size_t)idx;
-    colors[i3] = fmax_(sh_channel(a.D, sh, 0, x, y, z), 0.0f);
-    colors[i3 + 1] = fmax_(sh_channel(a.D, sh, 1, x, y, z), 0.0f);
-    colors[i3 + 2] = fmax_(sh_channel(a.D, sh, 2, x, y, z), 0.0f);
-}
-
-// dL_dsh gets every one of the M rows (zeros beyond the n used ones: it is the gradient of the full coefficient tensor);
-// dL_dpositions / dL_ddirections are optional.
-__global__ void __launch_bounds__(256) k_sh_to_rgb_bwd(ShRgbArgs a, const float* __restrict__ dL_dcolors,
-                                                       float* __restrict__ dL_dsh, float* __restrict__ dL_dpositions,
-                                                       float* __restrict__ dL_ddirections)
-{
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= a.P) return;
-    float x, y, z, vx, vy, vz, len;
-    sh_rgb_dir(a, idx, x, y, z, vx, vy, vz, len);
-    float sh[48], dsh[48];
-    load_sh_n(a.sh, idx, a.M, a.n, sh);
-#pragma unroll
-    for (int k = 0; k < 48; k++) dsh[k] = 0.0f;
-    const size_t i3 = 3 * (size_t)idx;
-    const float dcol[3] = {dL_dcolors[i3], dL_dcolors[i3 + 1], dL_dcolors[i3 + 2]};
-    // torch.clamp_min passes the gradient where the input is >= the bound
-    const uint32_t clamped = (sh_channel(a.D, sh, 0, x, y, z) < 0.f ? 1u : 0u) | (sh_channel(a.D, sh, 1, x, y, z) < 0.f ? 2u : 0u) |
-                             (sh_channel(a.D, sh, 2, x, y, z) < 0.f ? 4u : 0u);
-    float dL_ddir[3] = {0, 0, 0};
-    sh_backward(a.D, sh, dcol, clamped, x, y, z, dsh, dL_ddir);
-    if (dL_dsh) {
-        float* dst = dL_dsh + (size_t)idx * a.M * 3;
-        const int n_sh = 3 * a.M;
-        if (n_sh == 48 && ((uintptr_t)dst & 15) == 0) {
-            float4* d4 = reinterpret_cast<float4*>(dst);
-#pragma unroll
-            for (int i = 0; i < 12; i++) { float4 o = {dsh[4 * i], dsh[4 * i + 1], dsh[4 * i + 2], dsh[4 * i + 3]}; d4[i] = o; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 48; i++) if (i < n_sh) dst[i] = dsh[i];
-        }
-    }
-    if (a.positions) {
-        if (dL_dpositions) {
-            // d normalize(v) / dv = (I - n n^T) / |v|   (|v| above the eps of F.normalize)
-            const float dot = x * dL_ddir[0] + y * dL_ddir[1] + z * dL_ddir[2];
-            const float inv = 1.0f / len;
-            dL_dpositions[i3] = (dL_ddir[0] - x * dot) * inv;
-            dL_dpositions[i3 + 1] = (dL_ddir[1] - y * dot) * inv;
-            dL_dpositions[i3 + 2] = (dL_ddir[2] - z * dot) * inv;
-        }
-    } else if (dL_ddirections) {
-        dL_ddirections[i3] = dL_ddir[0]; dL_ddirections[i3 + 1] = dL_ddir[1]; dL_ddirections[i3 + 2] = dL_ddir[2];
-    }
 }
 
 }  // namespace
@@ -1436,72 +904,4 @@ void sgr_launch_masked_colors(int P, const GeomRec* rec, const float* acc, float
                               hipStream_t s)
 {
     hipLaunchKernelGGL(k_masked_colors, dim3((P + 255) / 256), dim3(256), 0, s, P, rec, acc, out, cam_pos, campos_row);
-}
-
-void sgr_launch_sh_adam_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,
-                                   const float* dcolor, float* sh, float* exp_avg, float* exp_avg_sq, float lr_dc, float lr_rest, float b1, float b2,
-                                   float eps, float bc1, float bc2_sqrt, float grad_scale, float* dmean_extra, hipStream_t s,
-                                   const uint32_t* guard, uint32_t guard_cap, uint8_t* reach)
-{
-    ShAdamArgs a = {lr_dc, lr_rest, b1, b2, sgr_one_minus(b1), sgr_one_minus(b2), eps, bc1, bc2_sqrt, grad_scale, guard, guard_cap, reach};
-    if (reach)  // (the callers have checked: M == 16, aligned buffers, no dmean_extra)
-        hipLaunchKernelGGL((k_sh_adam_from_views<false, true>), dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos,
-                           dcolor, sh, exp_avg, exp_avg_sq, a, dmean_extra);
-    else if (dmean_extra)
-        hipLaunchKernelGGL(k_sh_adam_from_views<true>, dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos, dcolor,
-                           sh, exp_avg, exp_avg_sq, a, dmean_extra);
-    else
-        hipLaunchKernelGGL(k_sh_adam_from_views<false>, dim3((P + 63) / 64), dim3(64), 0, s, P, V, D, M, vstride, means3D, campos, dcolor,
-                           sh, exp_avg, exp_avg_sq, a, dmean_extra);
-}
-
-void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s)
-{
-    if (job.P <= 0) return;
-    hipLaunchKernelGGL(k_sh_adam_zero, dim3((job.P + 63) / 64), dim3(64), 0, s, job);
-}
-
-void sgr_launch_sh_adam_zero_persistent(const SgrShAdamJob& job, hipStream_t s)
-{
-    if (job.P <= 0 || job.n_adam <= 0) return;
-    hipLaunchKernelGGL(k_sh_adam_zero_persistent, dim3(job.n_adam), dim3(64), 0, s, job);
-}
-
-void sgr_launch_sh_grad_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,
-                                   const float* dcolor, float* dL_dsh, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sh_grad_from_views, dim3((P + 255) / 256), dim3(256), 0, s, P, V, D, M, vstride, means3D, campos, dcolor,
-                       dL_dsh);
-}
-
-static int sh_rgb_args(ShRgbArgs& a, int P, int D, int M, const float* sh, const float* positions, const float* centers,
-                       int n_centers, const float* directions)
-{
-    if (D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16 || !sh) return SGR_E_INVALID;
-    if (positions ? (!centers || (n_centers != 1 && n_centers != P)) : !directions) return SGR_E_INVALID;
-    a.P = P; a.D = D; a.M = M; a.n = (D + 1) * (D + 1); a.sh = sh; a.positions = positions; a.centers = centers;
-    a.n_centers = n_centers; a.directions = directions;
-    return 0;
-}
-
-extern "C" int sgr_sh_to_rgb_forward(int P, int D, int M, const float* sh, const float* positions, const float* camera_centers,
-                                     int n_centers, const float* directions, float* colors, void* stream)
-{
-    if (P <= 0) return 0;
-    ShRgbArgs a;
-    if (!colors || sh_rgb_args(a, P, D, M, sh, positions, camera_centers, n_centers, directions) < 0) return SGR_E_INVALID;
-    hipLaunchKernelGGL(k_sh_to_rgb_fwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, colors);
-    return sgr_launch_status();
-}
-
-extern "C" int sgr_sh_to_rgb_backward(int P, int D, int M, const float* sh, const float* positions, const float* camera_centers,
-                                      int n_centers, const float* directions, const float* dL_dcolors, float* dL_dsh,
-                                      float* dL_dpositions, float* dL_ddirections, void* stream)
-{
-    if (P <= 0) return 0;
-    ShRgbArgs a;
-    if (!dL_dcolors || sh_rgb_args(a, P, D, M, sh, positions, camera_centers, n_centers, directions) < 0) return SGR_E_INVALID;
-    hipLaunchKernelGGL(k_sh_to_rgb_bwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, dL_dcolors, dL_dsh,
-                       dL_dpositions, dL_ddirections);
-    return sgr_launch_status();
 }

@@ -213,11 +213,26 @@ static inline void sgr_bias_corrections(float beta1, float beta2, int step, floa
     *bc2_sqrt = (float)sqrt(1.0 - pow(sgr_intended_double(beta2), (double)step));
 }
 
-// reach (M == 16, 16-byte aligned buffers only): the masked mode -- rows whose reach flag is 0 are left alone, the flags are cleared
+// One SH-Adam step as the host describes it: what the caller chose, and what the kernels receive in its place (1 - beta and the bias
+// corrections of `step`, formed in double as torch does).  Every caller of the SH-Adam launchers fills it through sgr_sh_adam_hyper.
+struct SgrShAdamHyper {
+    float lr_dc, lr_rest, beta1, beta2, eps, grad_scale;
+    const uint32_t* guard; uint32_t guard_cap;  // forward header + list capacity: the step is a no-op if that forward was invalid (NULL: no check)
+    float omb1, omb2, bc1, bc2_sqrt;            // derived
+};
+static inline SgrShAdamHyper sgr_sh_adam_hyper(float lr_dc, float lr_rest, float beta1, float beta2, float eps, int step, float grad_scale,
+                                               const uint32_t* guard = nullptr, uint32_t guard_cap = 0)
+{
+    SgrShAdamHyper h = {lr_dc, lr_rest, beta1, beta2, eps, grad_scale, guard, guard_cap, sgr_one_minus(beta1), sgr_one_minus(beta2), 0.f, 0.f};
+    sgr_bias_corrections(beta1, beta2, step, &h.bc1, &h.bc2_sqrt);
+    return h;
+}
+
+// reach (M == 16, 16-byte aligned buffers only, no dmean_extra): the masked mode -- rows whose reach flag is 0 are left alone, the
+// flags are cleared; NULL: every row
 void sgr_launch_sh_adam_from_views(int P, int V, int D, int M, size_t vstride, const float* means3D, const float* campos,
-                                   const float* dcolor, float* sh, float* exp_avg, float* exp_avg_sq, float lr_dc, float lr_rest, float b1, float b2,
-                                   float eps, float bc1, float bc2_sqrt, float grad_scale, float* dmean_extra, hipStream_t s,
-                                   const uint32_t* guard = nullptr, uint32_t guard_cap = 0, uint8_t* reach = nullptr);
+                                   const float* dcolor, float* sh, float* exp_avg, float* exp_avg_sq, const SgrShAdamHyper& h,
+                                   float* dmean_extra, uint8_t* reach, hipStream_t s);
 // The other half of the masked mode: the Adam update with a gradient of zero for the rows whose reach flag is 0 (sh_adam_update.h).
 // As a job it rides in the blend backward's launch as n_adam persistent workgroups in front of the blend's (sgr_launch_blend_bwd);
 // sgr_launch_sh_adam_zero is a launch of its own with one wave per 64 Gaussians, sgr_launch_sh_adam_zero_persistent the persistent
@@ -231,13 +246,17 @@ struct SgrShAdamJob {
     float zero;                  // 0.f, opaque to the compiler: the gradient
     const uint32_t* guard; uint32_t guard_cap;  // as ShAdamArgs: forward header + list capacity (NULL: no check)
 };
+// the job of one step over P Gaussians (n_adam: 0 for sgr_launch_sh_adam_zero, the persistent workgroups otherwise)
+static inline SgrShAdamJob sgr_sh_adam_job(const SgrShAdamHyper& h, int P, int n_adam, float* sh, float* exp_avg, float* exp_avg_sq,
+                                           const uint8_t* reach)
+{
+    return {P, n_adam, sh, exp_avg, exp_avg_sq, reach, h.lr_dc, h.lr_rest, h.beta1, h.beta2, h.omb1, h.omb2, h.eps, h.bc1, h.bc2_sqrt,
+            h.grad_scale, 0.f, h.guard, h.guard_cap};
+}
 void sgr_launch_sh_adam_zero(const SgrShAdamJob& job, hipStream_t s);
 void sgr_launch_sh_adam_zero_persistent(const SgrShAdamJob& job, hipStream_t s);  // job.n_adam one-wave workgroups
-#define SGR_ADAM_OVERLAP_DEFAULT 1
-#define SGR_ADAM_OVERLAP_WAVES_DEFAULT 512
-int sgr_adam_overlap();   // capi.hip: process-wide switch (sgr_set_adam_overlap)
-int sgr_rows_by_reach();  // capi.hip: process-wide switch (sgr_set_rows_by_reach)
-int sgr_adam_overlap_waves(); // capi.hip: SgrShAdamJob.n_adam (SGR_ADAM_OVERLAP_WAVES in the environment)
+// (the process-wide switches of the split -- sgr_set_adam_overlap, sgr_set_rows_by_reach, SGR_ADAM_OVERLAP_WAVES -- live in train.hip,
+// their only reader)
 // sgr_adam_step_ex with the same guard (adam.hip)
 int sgr_adam_launch(long long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n_seg,
                     const long long* seg_begin, const long long* seg_end, const float* seg_lr_a, const float* seg_lr_b,

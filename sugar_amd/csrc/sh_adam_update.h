@@ -1,4 +1,4 @@
-// sh_adam_update.h -- Adam on the SH block, split by reach flag (device code shared by preprocess.hip and blend.hip).
+// sh_adam_update.h -- Adam on the SH block, split by reach flag (device code shared by sh_adam.hip and blend.hip).
 //
 // The forward blend sets one byte per Gaussian that gets a survivor bit in any block (blend.hip).  The blend backward walks exactly
 // those bits, so a Gaussian whose flag is 0 receives no atomic: its nine accumulator sums stay zero, the backward preprocess takes
@@ -12,7 +12,7 @@
 #include "sgr_common.h"
 
 // The update of one SH coefficient.  Every operation is rounded on its own, in the order k_sh_adam_from_views has always had
-// (preprocess.hip is built without contraction: v_mul, v_mul, v_add per moment, IEEE sqrt and divides); the pragma keeps it so in a
+// (sh_adam.hip is built without contraction: v_mul, v_mul, v_add per moment, IEEE sqrt and divides); the pragma keeps it so in a
 // translation unit that contracts.
 __device__ __forceinline__ void sh_adam_update(float g, float& p, float& m, float& v, float lr, float grad_scale, float b1, float b2,
                                                float omb1, float omb2, float eps, float bc1, float bc2_sqrt)

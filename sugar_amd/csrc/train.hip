@@ -67,6 +67,32 @@ Rccl& rccl()
     return r;
 }
 
+// ---- the process-wide switches of sgr_trainer_step, their only reader
+// SH-Adam of unreached Gaussians inside the blend backward's launch (include/sugar_raster.h: sgr_set_adam_overlap); SGR_ADAM_OVERLAP
+// in the environment sets the default, SGR_ADAM_OVERLAP_WAVES the persistent Adam workgroups in front of the blend's (a multiple of 8)
+#define SGR_ADAM_OVERLAP_DEFAULT 1
+#define SGR_ADAM_OVERLAP_WAVES_DEFAULT 512
+int g_adam_overlap = -1;
+int sgr_adam_overlap()
+{
+    if (g_adam_overlap < 0) { const char* e = getenv("SGR_ADAM_OVERLAP"); g_adam_overlap = e ? (e[0] == '2' ? 2 : (e[0] != '0' ? 1 : 0)) : SGR_ADAM_OVERLAP_DEFAULT; }
+    return g_adam_overlap;
+}
+int sgr_adam_overlap_waves()  // SgrShAdamJob.n_adam
+{
+    const char* e = getenv("SGR_ADAM_OVERLAP_WAVES");  // (read per step: one getenv, and a test or an A/B run can change it in-process)
+    const int n = e ? atoi(e) : SGR_ADAM_OVERLAP_WAVES_DEFAULT;
+    return (n < 8 || (n & 7) || n > 65536) ? SGR_ADAM_OVERLAP_WAVES_DEFAULT : n;
+}
+// Backward preprocess of the train step by reach flag (include/sugar_raster.h: sgr_set_rows_by_reach); SGR_ROWS_BY_REACH=0 / 1 in the
+// environment sets the default (on)
+int g_rows_by_reach = -1;
+int sgr_rows_by_reach()
+{
+    if (g_rows_by_reach < 0) { const char* e = getenv("SGR_ROWS_BY_REACH"); g_rows_by_reach = (e && e[0] == '0') ? 0 : 1; }
+    return g_rows_by_reach;
+}
+
 }  // namespace
 
 struct sgr_trainer {
@@ -99,6 +125,11 @@ extern "C" {
 static thread_local std::string g_train_err;
 static int tfail(int code, const std::string& m) { g_train_err = m; return code; }
 const char* sgr_trainer_last_error(void) { return g_train_err.c_str(); }
+
+void sgr_set_rows_by_reach(int on) { g_rows_by_reach = on ? 1 : 0; }
+int sgr_get_rows_by_reach(void) { return sgr_rows_by_reach(); }
+void sgr_set_adam_overlap(int on) { g_adam_overlap = on == 2 ? 2 : (on ? 1 : 0); }
+int sgr_get_adam_overlap(void) { return sgr_adam_overlap(); }
 
 sgr_trainer* sgr_trainer_create(const sgr_train_config* cfg)
 {
@@ -198,6 +229,10 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
     // ... and the backward preprocess by the same flags: an unflagged Gaussian costs it two flag bytes (sgr_set_rows_by_reach)
     const bool by_reach = split && sgr_rows_by_reach() != 0;
     uint8_t* reach = reinterpret_cast<uint8_t*>(c.geom + sgr_geom_reach_offset(P));
+    // the SH-Adam step of ex->step, described once for both of its halves (a split step has phases == 15)
+    SgrShAdamHyper sh_hyper = {};
+    if ((phases & 12) && ex && ex->step >= 1)
+        sh_hyper = sgr_sh_adam_hyper(c.lr_features_dc, c.lr_features_rest, c.beta1, c.beta2, c.eps, ex->step, ex->grad_scale, header, cap);
     if (phases & 1) {
         if (!v->viewmatrix || !v->projmatrix || !v->campos || !v->gt_image) return tfail(SGR_E_INVALID, "sgr_trainer_step: null view");
         FixedBuf g = {c.geom, c.geom_bytes, 0}, b = {c.binning, c.binning_bytes, 0}, i = {c.img, c.img_bytes, 0};
@@ -249,13 +284,8 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
         SgrShAdamJob job = {};
         if (split) {
             if (ex->step < 1) return tfail(SGR_E_INVALID, "sgr_trainer_step: exchange description missing");
-            job.P = P; job.n_adam = sgr_adam_overlap_waves();
-            job.sh = flat + c.off_features; job.exp_avg = c.exp_avg + c.off_features; job.exp_avg_sq = c.exp_avg_sq + c.off_features;
-            job.reach = reach;
-            job.lr_dc = c.lr_features_dc; job.lr_rest = c.lr_features_rest; job.b1 = c.beta1; job.b2 = c.beta2;
-            job.omb1 = sgr_one_minus(c.beta1); job.omb2 = sgr_one_minus(c.beta2); job.eps = c.eps; job.grad_scale = ex->grad_scale;
-            job.zero = 0.f; job.guard = header; job.guard_cap = cap;
-            sgr_bias_corrections(c.beta1, c.beta2, ex->step, &job.bc1, &job.bc2_sqrt);
+            job = sgr_sh_adam_job(sh_hyper, P, sgr_adam_overlap_waves(), flat + c.off_features, c.exp_avg + c.off_features,
+                                  c.exp_avg_sq + c.off_features, reach);
         }
         // compact SH mode (dL_dsh == NULL), raw-parameter gradients straight into the flat gradient buffer.  Both halves asked
         // for at once (no collective to start in between): ONE pass, the preprocess kernel writes the masked colour gradients
@@ -281,8 +311,6 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
     }
     if (phases & 12) {
         if (!ex || ex->step < 1 || ex->n_views < 1) return tfail(SGR_E_INVALID, "sgr_trainer_step: exchange description missing");
-        float bc1, bc2_sqrt;
-        sgr_bias_corrections(c.beta1, c.beta2, ex->step, &bc1, &bc2_sqrt);
         if (phases & 4) {
             const float* cols = ex->all_colors ? ex->all_colors : c.colors;
             const float* cams = ex->all_campos ? ex->all_campos : (ex->all_colors ? nullptr : c.colors + 3 * (size_t)P);
@@ -297,8 +325,7 @@ int sgr_trainer_step(sgr_trainer* t, const sgr_train_view* v, int phases, const 
             SgrStageTimer tm(s, SGR_STAGE_SH_ADAM);
             sgr_launch_sh_adam_from_views((int)(g1 - g0), ex->n_views, c.D, c.M, stride, means3D + 3 * (size_t)g0, cams, cols,
                                           flat + c.off_features + fo, c.exp_avg + c.off_features + fo, c.exp_avg_sq + c.off_features + fo,
-                                          c.lr_features_dc, c.lr_features_rest, c.beta1, c.beta2, c.eps, bc1, bc2_sqrt, ex->grad_scale, nullptr, s,
-                                          header, cap, split ? reach : nullptr);  // (split: the flagged rows only; clears the flags)
+                                          sh_hyper, nullptr, split ? reach : nullptr, s);  // (split: the flagged rows only; clears the flags)
             tm.stop();
             if (hipGetLastError() != hipSuccess) return tfail(SGR_E_HIP, "sh_adam launch failed");
         }

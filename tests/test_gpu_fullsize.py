@@ -274,7 +274,7 @@ def test_the_headline_path_itself_matches_the_reference_at_the_metric_size():
     xyz, raw_op, raw_sc, raw_q, shs = seg("xyz", (P, 3)), seg("opacity", (P, 1)), seg("scaling", (P, 3)), seg("rotation", (P, 4)), \
         seg("features", (P, params.M, 3))
     # the activated values the preprocess kernel forms on the fly, bit for bit: the stand-alone activation kernels carry the same
-    # arithmetic operation for operation (csrc/preprocess.hip:274-281), so both sides start from identical inputs
+    # arithmetic operation for operation (csrc/preprocess.hip:125-132), so both sides start from identical inputs
     from sugar_amd.train_step import _Activations
     with torch.no_grad():
         scales, rots, opac = _Activations.apply(raw_sc.contiguous(), raw_q.contiguous(), raw_op.contiguous(), None)

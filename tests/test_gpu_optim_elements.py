@@ -375,7 +375,7 @@ def test_sh_gradient_and_its_adam_every_element(name):
 @pytest.mark.parametrize("name", ["P65-D3M16", "P130-D2M16", "P130-some", "P1-D3M16"])
 def test_sh_adam_fused_against_gradient_then_flat_adam(name):
     """sgr_sh_grad_from_views, then sgr_adam_step over the [P, 48] block with one periodic segment (48, 3): held to the same bars as
-    the fused kernel (not bit for bit: preprocess.hip is built without contraction, adam.hip with)"""
+    the fused kernel (not bit for bit: sh_adam.hip is built without contraction, adam.hip with)"""
     c, i = oc.SH[name], oc.sh_inputs(name)
     a = oc.SH_ARGS
     grad = _sh_grad_run(name)
